@@ -21,9 +21,13 @@ is not already running under torch.distributed.run; sequences are sharded, every
 a private cache (weak scaling: the same per-rank workload; ``--scaling strong`` splits a
 fixed batch); the only collective is the reduction of the throughput scalars.
 
-Prints ONE compact JSON line (rank 0, < 4 KB, the last line of stdout): the contract's keys, `roofline`,
-`cpu_baseline`, the parity verdict.  The legs that do not fit it (other configurations, engine-sized cache, call
-forms, S0 stages, adjacent attention) go to ``--detail-json`` (default bench_detail.json), named in the line.
+Prints ONE compact JSON line (rank 0, < 4 KB, the last line of stdout).  A plain run sets up, warms up, times
+``--steps`` steps and prints the contract's keys, the stage times and the compaction kernel's `roofline` from the
+events of those steps -- nothing else.  ``--full`` adds everything that takes work of its own: the parity gate (the
+oracle on the timed workload), `cpu_baseline`, the live PMC traffic, the access-pattern probe and the side legs
+(other configurations, engine-sized cache, call forms, S0 stages, adjacent attention, native layout), which go to
+``--detail-json`` (default bench_detail.json), named in the line.  ``--dump-outputs DIR`` writes what the last timed
+step computed as DIR/<name>.npy, so that two builds can be compared output for output.
 The timed step calls the path exactly as the fork's scheduler does (``--call-form fork``).
 """
 from __future__ import annotations
@@ -54,11 +58,22 @@ CONFIGS = {     # BASELINE.json configs[1..4]; c2 is the configuration the metri
 }
 
 
+DUMP_MAX_BYTES_PER_ARRAY = 6 << 20      # nine arrays: 54 MiB at the most
+
+
 def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the parity gate, cpu_baseline, live PMC traffic, the pattern probe, "
+                         "the side legs and the detail file (the --no-* / --headline-only flags below trim a --full run; a "
+                         "run without --full does none of it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last step computed -- the arrays the path's caller receives -- "
+                         "as DIR/<name>.npy (float32 / float64; a fixed seeded sample of an array above "
+                         f"{DUMP_MAX_BYTES_PER_ARRAY >> 20} MiB)")
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS),
                     help="BASELINE.json configuration (explicit shape flags override it)")
     ap.add_argument("--layers", type=int, default=None)
@@ -129,6 +144,8 @@ def parse_args(argv=None):
     ap.add_argument("--traffic-json", default=os.path.join(REPO, "profiles", "traffic.json"),
                     help="PMC-derived HBM bytes per launch of the compaction kernel, if collected")
     args = ap.parse_args(argv)
+    if args.dump_outputs and args.lean:
+        ap.error("--dump-outputs with --lean: the rows no consumer reads are left undefined, two runs need not agree on them")
     preset = CONFIGS[args.config]
     for key, default in (("layers", 32), ("block_size", 16), ("seq_len", 32768), ("batch", 1),
                          ("kv_dtype", "fp16"), ("steady_cap", 0), ("keep", 0.5)):
@@ -1370,12 +1387,12 @@ def cpu_baseline(args):
 def native_layout_run(args, timeout=900):
     """The same workload with slot-major cache blocks (KVC_BLOCK_LAYOUT=slot_major: K [bs][hd], V [bs][hd] inside every
     block; tensor shapes, op signatures, slot numbers unchanged), measured by this same script in a child process
-    (`--block-layout slot_major --headline-only`): the compaction kernel's roofline object, the step's stage times and the
+    (`--full --block-layout slot_major --headline-only`): the compaction kernel's roofline object, the step's stage times and the
     parity verdict (the compacted cache, permuted back, against the oracle).  None if the child fails."""
     import copy
     a2 = copy.copy(args)
     a2.block_layout = "slot_major"
-    cmd = ([sys.executable, os.path.abspath(__file__), "--steps", str(min(args.steps, 20)), "--warmup", "3",
+    cmd = ([sys.executable, os.path.abspath(__file__), "--full", "--steps", str(min(args.steps, 20)), "--warmup", "3",
             "--headline-only", "--no-cpu-baseline", "--no-probe", "--detail-json", "", "--spare-blocks", str(args.spare_blocks)]
            + workload_flags(a2) + (["--no-live-traffic"] if args.no_live_traffic else []))
     try:
@@ -1479,9 +1496,37 @@ def emit(res, detail_path):
     print(compact_line(res, detail_path), flush=True)
 
 
+def dump_outputs(path, arrays):
+    """``--dump-outputs``: every array the last timed step handed its caller as ``path/<name>.npy``.  Integers go out
+    as float64 (exact), the metric store as the float32 it is, K / V as the VALUES OF THEIR ELEMENTS' BIT PATTERNS in
+    float32 (0 .. 65535, exact: the compaction copies bytes, and the synthetic cache holds random bits -- NaNs as
+    fp16 numbers, which no comparison survives).  An array above DUMP_MAX_BYTES_PER_ARRAY on disk is sampled: the
+    elements at fixed, seeded flat indices (the same for every run of the same shape), in ascending order."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    for name, t in arrays.items():
+        if t.dtype in (torch.float16, torch.bfloat16):
+            t = t.view(torch.int16)
+        bits = t.dtype in (torch.int16, torch.uint8)       # a cache plane
+        out_dtype = np.float32 if (bits or t.dtype == torch.float32) else np.float64
+        flat = t.reshape(-1)
+        keep = DUMP_MAX_BYTES_PER_ARRAY // np.dtype(out_dtype).itemsize
+        if flat.numel() > keep:
+            idx = np.sort(np.random.default_rng(0).integers(0, flat.numel(), size=keep, dtype=np.int64))
+            flat = flat[torch.from_numpy(idx).to(flat.device)]
+        a = flat.cpu().numpy()
+        if a.dtype == np.int16:
+            a = a.view(np.uint16)
+        np.save(os.path.join(path, name + ".npy"), a.astype(out_dtype))
+
+
 # --------------------------------------------------------------------------- main
 def main():
     args = parse_args()
+    if not args.full:
+        # a plain run does what its headline needs: set-up, warm-up, the timed steps, the line
+        args.headline_only = args.no_parity_gate = args.no_cpu_baseline = args.no_live_traffic = args.no_probe = True
+        args.detail_json = ""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))
@@ -1622,6 +1667,13 @@ def main():
     gc.enable()
     elapsed = t1 - t0
     kernel_ms = sum(m[3].elapsed_time(m[4]) for m in marks) / args.steps
+    if args.dump_outputs and rank == 0:
+        # what the fork's scheduler holds after the three calls: the schedule, the move list, and the cache, metric
+        # store and positions that execute_cache_moves compacted in place
+        dump_outputs(args.dump_outputs, {
+            "evicted_logical_indices": out["eli"], "evicted_kv_count": out["ekc"], "evicted_block_count": out["ebc"],
+            "cache_moves_idx": out["cmi"], "cache_moves_count": out["cmc"], "k_cache": k_cache, "v_cache": v_cache,
+            "kv_metrics": work_metrics, "kv_position": work_pos})
 
     evicted_slots = int(out["ekc"].sum().item())
     cmc, ekc_ref = out["cmc"], out["ekc"]

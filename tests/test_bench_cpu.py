@@ -51,6 +51,23 @@ def test_cpu_baseline_leg_runs_on_all_cores():
     assert c["single_core_port"]["cores"] == 1 and c["single_core_port"]["value"] > 0
 
 
+def test_dump_outputs_is_exact_and_samples_the_same_elements_every_time(tmp_path):
+    small = torch.arange(-5, 2 ** 24 + 3, 2 ** 21, dtype=torch.int32)                  # past float32's exact integers
+    bits = torch.tensor([0x7e00, 0xfc00, 0x3c00, 0x0001], dtype=torch.int32).to(torch.int16).view(torch.float16)   # NaN, -inf, 1, denormal
+    n = bench.DUMP_MAX_BYTES_PER_ARRAY // 4 * 3 + 7
+    big = torch.arange(n, dtype=torch.float32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"small": small, "bits": bits, "fp8": bits.view(torch.uint8), "big": big})
+    got = {f.stem: np.load(f) for f in (tmp_path / "a").iterdir()}
+    assert got["small"].dtype == np.float64 and np.array_equal(got["small"], small.numpy())
+    assert got["bits"].dtype == np.float32 and got["bits"].tolist() == [0x7e00, 0xfc00, 0x3c00, 0x0001]
+    assert got["fp8"].tolist() == [0x00, 0x7e, 0x00, 0xfc, 0x00, 0x3c, 0x01, 0x00]
+    assert got["big"].dtype == np.float32 and got["big"].nbytes == bench.DUMP_MAX_BYTES_PER_ARRAY
+    assert np.all(np.diff(got["big"]) >= 0) and got["big"].max() < n and got["big"].max() > 0.99 * n
+    for name, a in got.items():
+        assert np.array_equal(a, np.load(tmp_path / "b" / (name + ".npy"))), name
+
+
 def test_self_launch_command(monkeypatch):
     seen = {}
 

@@ -25,7 +25,7 @@ def test_single_rank_line(tmp_path):
     """the LAST stdout line is the compact one the driver parses (< 4 KB: round 5's 22 KB line was not parsed); the
     legs that do not fit it are in the detail file the line names"""
     detail = tmp_path / "detail.json"
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "4", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "4", "--warmup", "1",
                           "--seq-len", "4096", "--no-adjacent", "--engine-cache-frac", "0.02", "--no-live-traffic",
                           "--detail-json", str(detail)],
                          capture_output=True, text=True, timeout=600, cwd=REPO,
@@ -74,13 +74,45 @@ def test_single_rank_line(tmp_path):
 
 
 def test_headline_only_line():
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                           "--seq-len", "2048", "--headline-only", "--no-live-traffic", "--detail-json", ""],
                          capture_output=True, text=True, timeout=600, cwd=REPO)
     assert out.returncode == 0, out.stderr[-2000:]
     d = _last_json(out.stdout)
     assert KEYS <= set(d) and "cpu_baseline" in d and d["parity_checked"]["bit_exact"] is True
     assert "stages_ms_hinted" not in d and "other_configs" not in d and d["detail"] is None
+
+
+def test_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """without --full: the timed steps and the line -- no oracle, no cpu_baseline, no side leg, no detail file -- and
+    --dump-outputs writes what the last step handed its caller (the line's own counts are the sums of the dumped ones)"""
+    import numpy as np
+    import bench
+    dump = tmp_path / "dump"
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--seq-len", "2048", "--layers", "4", "--dump-outputs", str(dump)],
+                         capture_output=True, text=True, timeout=600, cwd=tmp_path)
+    assert out.returncode == 0, out.stderr[-2000:]
+    d = _last_json(out.stdout)
+    assert KEYS <= set(d) and d["steps"] == 3 and d["warmup"] == 1 and d["ms_per_step"] > 0 and d["dtype"] == "u8"
+    assert d["unit"] == "KV slots/s" and d["higher_is_better"] is True and 0 < d["roofline"]["frac"] < 1
+    units = d["config"]["evicted_slots"] + d["config"]["moved_slots"]
+    assert abs(d["value"] - units / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-4
+    assert d["parity_checked"] is None and d["detail"] is None and not list(tmp_path.glob("*.json"))
+    for k in ("cpu_baseline", "stages_ms_hinted", "roofline_native_layout", "other_configs"):
+        assert k not in d, k
+    arrays = {f.stem: np.load(f) for f in dump.iterdir()}
+    assert set(arrays) == {"evicted_logical_indices", "evicted_kv_count", "evicted_block_count", "cache_moves_idx",
+                           "cache_moves_count", "k_cache", "v_cache", "kv_metrics", "kv_position"}
+    assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+    assert np.isfinite(arrays["k_cache"]).all() and np.isfinite(arrays["v_cache"]).all()      # (bit patterns, not fp16 values)
+    assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 << 20
+    assert arrays["evicted_kv_count"].sum() == d["config"]["evicted_slots"]
+    assert arrays["cache_moves_count"].sum() == d["config"]["moved_slots"]
+    assert arrays["evicted_block_count"].sum() == d["config"]["freed_blocks"]
+    # L4 H8, 2048 tokens: the caches are sampled, the schedule's arrays are whole
+    assert arrays["evicted_kv_count"].shape == (1 * 4 * 8,) and arrays["cache_moves_idx"].size == 2 * d["config"]["candidate_slots"]
+    assert arrays["k_cache"].size == arrays["v_cache"].size == bench.DUMP_MAX_BYTES_PER_ARRAY // 4
 
 
 @pytest.mark.parametrize("launcher", ["self", "torchrun"])
@@ -178,7 +210,7 @@ def test_default_line_carries_the_other_configurations(tmp_path):
     detail = tmp_path / "detail.json"
     out = subprocess.run([sys.executable, "-c",
                           "import bench, sys; bench.OTHER_CONFIGS = (('c5', 2, 1), ('c3', 2, 1)); "
-                          "sys.argv = ['bench.py', '--steps', '3', '--warmup', '1', '--no-adjacent', '--no-s0', "
+                          "sys.argv = ['bench.py', '--full', '--steps', '3', '--warmup', '1', '--no-adjacent', '--no-s0', "
                           "'--no-cpu-baseline', '--no-engine-cache', '--no-probe', '--no-live-traffic', "
                           f"'--detail-json', {str(detail)!r}]; bench.main()"],
                          capture_output=True, text=True, timeout=900, cwd=REPO,
@@ -228,7 +260,7 @@ def test_engine_leg_traffic_is_measured_live(tmp_path):
     import shutil
     if shutil.which("rocprofv3") is None and not os.path.exists("/opt/rocm/bin/rocprofv3"):
         pytest.skip("no rocprofv3 on this box")
-    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--steps", "3", "--warmup", "1",
+    out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--steps", "3", "--warmup", "1",
                           "--seq-len", "4096", "--no-adjacent", "--no-s0", "--no-cpu-baseline", "--no-probe",
                           "--engine-cache-frac", "0.02", "--detail-json", str(tmp_path / "detail.json")],
                          capture_output=True, text=True, timeout=900, cwd=REPO)
