@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 8
+#define KVC_ABI_VERSION 9
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -788,6 +788,61 @@ int32_t kvc_paged_attention_decode_uses_partitions_in(int32_t num_seqs, int32_t 
                                                       int32_t num_kv_heads, int32_t head_size,
                                                       int32_t max_context_len, int32_t schedule,
                                                       int32_t block_layout);
+
+/* ---------------------------------------------------------------------------------
+ * F5  query-block ("chunk") paged attention over the per-head cache, with KV-metric output (ABI version 9)
+ * Not in the reference: its prefix-enabled prefill branch (vllm/attention/backends/flash_attn.py:1046-1063)
+ * hands the cache and ONE block table per sequence to flash_attn_varlen_func, which cannot read a cache that
+ * has one block table, one context length and a sparse set of positions per (sequence, KV head).  This op is
+ * what runs MORE THAN ONE new token per sequence over such a cache: chunked prefill, a follow-up turn on a
+ * kept cache, prefix reuse, verifying k draft tokens.
+ * Sequence s owns query tokens query_start_loc[s] .. query_start_loc[s + 1] - 1 (nq_s of them, 0 allowed).
+ * Their K/V have already been written (kvc_reshape_and_cache*): they are the LAST nq_s logical slots of every
+ * head of the sequence, and context_lens counts them (as it counts the current token in decode).  Token j
+ * (0-based inside its sequence) sees, of KV head h, logical slots i < max(0, context_lens[s, h] - (nq_s - 1 - j));
+ * with nq_s = 1 that is the decode rule.
+ *   out[t, q, :] = softmax(scale * query[t, q] . K^T) . V over the visible slots: plain softmax (no + 1e-6),
+ *   statistics and accumulation in fp32, rounded once to dtype.  A row that sees nothing is 0.  Every
+ *   element of out of every token is written.
+ *   metrics (optional, [num_blocks, block_size] float): for every slot of the sequence's heads
+ *   metrics[slot] += sum p^2 (use_l2) or sum p, over the query heads of the slot's KV head and the tokens t
+ *   that see the slot with kv_position[slot] <= query_positions[t] - kv_metric_buffer_len[s] -- what nq_s
+ *   decode steps with fused_metrics would have added.  One writer per slot, a sum formed in a fixed order, no
+ *   atomics: identical from run to run.  Slots no token reaches, and all other blocks, are not written.
+ * dtype 0 = fp16, 1 = bf16 (query, out and the cache).  KVC_ERR_INVALID, nothing launched: fp8 caches
+ * (kv_cache_dtype != 0), alibi_slopes != NULL, head_size other than 64 / 128, block_size other than 16 / 32,
+ * num_heads % num_kv_heads != 0, query rows that are not 16-byte aligned (out rows: 8-byte).  Any
+ * num_heads / num_kv_heads >= 1.  Grids are sized from max_query_len and max_context_len (nothing is read back);
+ * tokens past max_query_len and slots past max_context_len are ignored.  num_seqs = 0 / no tokens: no-op.
+ * workspace: the row statistics, the _workspace_bytes companion says how much (8-byte aligned).
+ * --------------------------------------------------------------------------------- */
+typedef struct kvc_attention_chunk_params {
+  void* out;                            /* [num_tokens, num_heads, head_size], token stride out_stride */
+  float* metrics;                       /* optional (may be NULL): [num_blocks, block_size] */
+  const void* query;                    /* [num_tokens, num_heads, head_size], token stride q_stride */
+  const void* key_cache;                /* as kvc_attention_params */
+  const void* value_cache;
+  const int32_t* block_tables;          /* [num_seqs, num_kv_heads, max_num_blocks_per_seq] */
+  const int32_t* context_lens;          /* [num_seqs, num_kv_heads] */
+  const int32_t* kv_position;           /* [num_blocks, block_size] */
+  const int32_t* query_start_loc;       /* [num_seqs + 1], ascending, [0] .. [num_seqs] <= num_tokens */
+  const int32_t* query_positions;       /* [num_tokens] */
+  const int32_t* kv_metric_buffer_len;  /* [num_seqs] */
+  const float* alibi_slopes;            /* must be NULL */
+  void* workspace;
+  size_t workspace_bytes;
+  int64_t q_stride, out_stride;         /* elements between tokens */
+  int64_t kv_block_stride;              /* elements between blocks of the caches */
+  float scale;
+  int32_t num_seqs, num_tokens, num_heads, num_kv_heads, head_size, block_size;
+  int32_t max_num_blocks_per_seq, max_context_len, max_query_len;
+  int32_t dtype, kv_cache_dtype;
+  int32_t use_l2;                       /* metrics: accumulate p^2 (1) or p (0) */
+  int32_t block_layout;                 /* KVC_LAYOUT_* */
+} kvc_attention_chunk_params;
+
+size_t kvc_paged_attention_chunk_workspace_bytes(int32_t num_tokens, int32_t num_heads);
+int kvc_paged_attention_chunk(const kvc_attention_chunk_params* p, kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

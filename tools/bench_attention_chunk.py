@@ -1,0 +1,125 @@
+#!/usr/bin/env python3
+"""Query-block attention over the per-head cache (F5, paged_attention_kvc_chunk) against the only other way this
+package can produce the same result: nq successive calls of the decode op with trimmed context lengths.
+
+Llama-3-8B heads (32 query / 8 KV, head size 128, block size 16), batch 16, contexts 4k and 32k, nq 16 / 64 / 256,
+with and without the metric, in both block layouts.  Times are medians of device-event timings after warm-up; the
+algorithmic traffic of the chunk op is 2 * hd * e bytes per visible slot and query tile (16 tokens), reported as a
+fraction of 8 TB/s.  Run on the GPU box:  python tools/bench_attention_chunk.py [--json out.json] [--only ctx,nq]"""
+import argparse
+import json
+import os
+import statistics
+import sys
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+import torch  # noqa: E402
+
+import vllm_kvcompress_amd as kvc  # noqa: E402
+from vllm_kvcompress_amd import _custom_ops as ops  # noqa: E402
+
+S, HQ, HKV, HD, BS, TILE, PEAK = 16, 32, 8, 128, 16, 16, 8e12
+
+
+def timed(fn, warmup, reps):
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        a.record()
+        fn()
+        b.record()
+        b.synchronize()
+        ms.append(a.elapsed_time(b))
+    return statistics.median(ms), min(ms), max(ms)
+
+
+def make_cache(ctx, dev, gen):
+    nblk = (ctx + BS - 1) // BS
+    NB = S * HKV * nblk
+    kc = torch.randn((NB, HD // 8, BS, 8), device=dev, generator=gen, dtype=torch.float16)
+    vc = torch.randn((NB, HD, BS), device=dev, generator=gen, dtype=torch.float16)
+    bt = torch.randperm(NB, device=dev, generator=gen).to(torch.int32).view(S, HKV, nblk)
+    lens = torch.full((S, HKV), ctx, dtype=torch.int32, device=dev)
+    # positions: slot i of every head holds token i (an uncompressed history: every slot inside the window)
+    pos = torch.zeros((NB, BS), dtype=torch.int32, device=dev)
+    pos[bt.long().view(-1)] = torch.arange(nblk * BS, dtype=torch.int32, device=dev).view(1, nblk, BS).expand(
+        S * HKV, nblk, BS).reshape(-1, BS)
+    return kc, vc, bt, lens, pos
+
+
+def run(ctx, nq, with_metric, state, dev, gen):
+    kc, vc, bt, lens, pos = state
+    T = S * nq
+    q = torch.randn((T, HQ, HD), device=dev, generator=gen, dtype=torch.float16)
+    out = torch.empty_like(q)
+    qsl = torch.arange(0, T + 1, nq, dtype=torch.int32, device=dev)
+    qpos = (torch.arange(nq, dtype=torch.int32, device=dev) + (ctx - nq)).repeat(S)
+    buf = torch.zeros(S, dtype=torch.int32, device=dev)
+    metrics = torch.zeros(pos.shape, dtype=torch.float32, device=dev) if with_metric else None
+    scale = HD ** -0.5
+
+    def chunk():
+        ops.paged_attention_kvc_chunk(out, q, kc, vc, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
+                                      metrics=metrics, use_l2=True)
+
+    # the decode baseline: step j sees context_lens - (nq - 1 - j) slots and has one query per sequence
+    q4, out_d = q.view(S, nq, HQ, HD), torch.empty((S, HQ, HD), dtype=q.dtype, device=dev)
+    step_lens = [(lens - (nq - 1 - j)).contiguous() for j in range(nq)]
+    step_last = [torch.full((S,), ctx - nq + j, dtype=torch.int32, device=dev) for j in range(nq)]
+    temp = torch.empty(pos.shape + (HQ // HKV,), dtype=torch.float32, device=dev)
+
+    def decode():
+        for j in range(nq):
+            if with_metric:
+                ops.paged_attention_kvc_fused_metrics(out_d, metrics, q4[:, j], kc, vc, HKV, scale, bt, step_lens[j], pos,
+                                                      step_last[j], buf, BS, ctx, None, "auto", 1.0, 1.0, use_l2=True,
+                                                      temp_metrics=temp)
+            else:
+                ops.paged_attention_kvc_v1(out_d, temp, q4[:, j], kc, vc, HKV, scale, bt, step_lens[j], pos,
+                                           step_last[j], buf, BS, ctx, None, "auto", 1.0, 1.0, False)
+
+    c_ms, c_lo, c_hi = timed(chunk, 3, 20)
+    d_ms, d_lo, d_hi = timed(decode, 1, 5)
+    tiles = (nq + TILE - 1) // TILE
+    visible = sum(max(0, ctx - (nq - 1 - min(nq, TILE * (t + 1)) + 1)) for t in range(tiles))    # per head
+    byts = S * HKV * visible * 2 * HD * 2
+    return dict(layout=kvc.block_layout(), batch=S, ctx=ctx, nq=nq, metrics=with_metric, chunk_ms=c_ms, chunk_ms_min=c_lo,
+                chunk_ms_max=c_hi, decode_x_nq_ms=d_ms, decode_x_nq_ms_min=d_lo, decode_x_nq_ms_max=d_hi,
+                speedup=d_ms / c_ms, chunk_algorithmic_bytes=byts, chunk_fraction_of_8TBps=byts / (c_ms * 1e-3) / PEAK)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--json", default=None)
+    ap.add_argument("--only", default=None, help="ctx,nq: a single configuration")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        raise SystemExit("bench_attention_chunk: needs a GPU (nothing is estimated)")
+    dev = "cuda:0"
+    gen = torch.Generator(device=dev)
+    gen.manual_seed(0)
+    cfgs = [(c, n) for c in (4096, 32768) for n in (16, 64, 256)]
+    if args.only:
+        cfgs = [tuple(int(v) for v in args.only.split(","))]
+    res = []
+    for ctx in sorted({c for c, _ in cfgs}):
+        state = make_cache(ctx, dev, gen)
+        for layout in ("reference", "slot_major"):
+            kvc.set_block_layout(layout)          # (random values: the same buffers serve either layout)
+            for nq in [n for c, n in cfgs if c == ctx]:
+                for with_metric in (False, True):
+                    r = run(ctx, nq, with_metric, state, dev, gen)
+                    res.append(r)
+                    print(json.dumps(r), flush=True)
+        del state
+    kvc.set_block_layout("reference")
+    if args.json:
+        json.dump(res, open(args.json, "w"), indent=1)
+
+
+if __name__ == "__main__":
+    main()

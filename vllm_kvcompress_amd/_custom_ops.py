@@ -668,3 +668,88 @@ def paged_attention_kvc_v2(out, kv_metric_out, exp_sum, max_logits, tmp_out, tmp
                          context_lens, kv_position, last_position, kv_metric_buffer_len,
                          block_size, max_context_len, alibi_slopes, kv_cache_dtype, k_scale,
                          v_scale, record_kv_metrics)
+
+
+# ---------------------------------------------------------------------------------------
+# F5: query-block attention over the per-head cache (not in the reference: its prefix-enabled
+# prefill branch, vllm/attention/backends/flash_attn.py:1046-1063, cannot read a per-head cache)
+def reserve_attention_chunk_scratch(device, num_tokens: int, num_heads: int) -> None:
+    """Pre-size the row-statistics scratch of ``paged_attention_kvc_chunk`` for the largest token batch the
+    engine will run, so the op never allocates while serving or inside a HIP-graph capture."""
+    reserve_workspace(torch.device(device), _lib.load().kvc_paged_attention_chunk_workspace_bytes(
+        int(num_tokens), int(num_heads)) + 256, "attn_chunk")
+
+
+def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: int, scale: float,
+                              block_tables, context_lens, kv_position, query_start_loc, query_positions,
+                              kv_metric_buffer_len, block_size: int, max_context_len: int,
+                              max_query_len: int, metrics: Optional[torch.Tensor] = None,
+                              use_l2: bool = True, alibi_slopes=None, kv_cache_dtype: str = "auto") -> None:
+    """Attention of ``nq_s >= 0`` new tokens per sequence over the per-head paged cache (chunked prefill, a
+    follow-up turn on a kept cache, prefix reuse, verifying draft tokens): ``query`` / ``out``
+    ``[num_tokens, num_heads, head_size]`` packed over the sequences, sequence ``s`` owning tokens
+    ``query_start_loc[s] .. query_start_loc[s + 1] - 1``.  The new tokens' K/V are in the cache already
+    (``reshape_and_cache_kvc``) as the last ``nq_s`` logical slots of every head, and ``context_lens`` counts
+    them; token ``j`` of its sequence sees slots ``i < max(0, context_lens[s, h] - (nq_s - 1 - j))``.
+    With ``metrics [num_blocks, block_size]``: ``+= sum p^2`` (``use_l2``) or ``sum p`` per slot over the KV
+    head's query heads and the tokens ``t`` that see the slot with ``kv_position[slot] <= query_positions[t] -
+    kv_metric_buffer_len[s]`` -- what ``nq_s`` calls of ``paged_attention_kvc_fused_metrics`` would have added,
+    formed in a fixed order (identical from run to run).  ``alibi_slopes`` and fp8 caches are refused
+    (include/kvc_mi355x.h, F5)."""
+    lib = _lib.load()
+    for name, t in (("out", out), ("query", query), ("key_cache", key_cache), ("value_cache", value_cache)):
+        _require(t, name)
+    if metrics is not None:
+        _require(metrics, "metrics", torch.float32)
+        if not metrics.is_contiguous():
+            raise RuntimeError("paged_attention_kvc: metrics must be contiguous (updated in place)")
+    for name, t in (("block_tables", block_tables), ("context_lens", context_lens),
+                    ("kv_position", kv_position), ("query_start_loc", query_start_loc),
+                    ("query_positions", query_positions), ("kv_metric_buffer_len", kv_metric_buffer_len)):
+        _require(t, name, torch.int32)
+    kvds = {"auto": 0, "fp8": 1, "fp8_e4m3": 1, "fp8_e5m2": 2}
+    if kv_cache_dtype not in kvds:
+        raise RuntimeError(f"Unsupported data type of kv cache: {kv_cache_dtype}")
+    dtypes = {torch.float16: 0, torch.bfloat16: 1}
+    if query.dtype not in dtypes:
+        raise RuntimeError(f"Unsupported data type: {query.dtype}")
+    if out.dtype != query.dtype:
+        raise RuntimeError("paged_attention_kvc: query and output must share a dtype")
+    if kv_cache_dtype == "auto" and (key_cache.dtype != query.dtype or value_cache.dtype != query.dtype):
+        raise RuntimeError("paged_attention_kvc: an \"auto\" cache has the query's dtype")
+    num_tokens, num_heads, head_size = query.shape
+    if query.stride(1) != head_size or query.stride(2) != 1:
+        raise RuntimeError("paged_attention_kvc: query must be contiguous in (head, dim)")
+    if out.shape != query.shape or out.stride(1) != head_size or out.stride(2) != 1:
+        raise RuntimeError("paged_attention_kvc: out must have the query's shape, contiguous in (head, dim)")
+    num_seqs = query_start_loc.numel() - 1
+    if context_lens.numel() != max(num_seqs, 0) * int(num_kv_heads) or query_positions.numel() != num_tokens:
+        raise RuntimeError("paged_attention_kvc_chunk: context_lens is [num_seqs, num_kv_heads] and "
+                           "query_positions [num_tokens], num_seqs = len(query_start_loc) - 1")
+    keep = []
+    bt = _contig(block_tables, keep)
+    p = _lib.KvcAttentionChunkParams()
+    p.out, p.metrics = out.data_ptr(), _ptr(metrics)
+    p.query, p.key_cache, p.value_cache = query.data_ptr(), key_cache.data_ptr(), value_cache.data_ptr()
+    p.block_tables = bt.data_ptr()
+    p.context_lens = _contig(context_lens, keep).data_ptr()
+    p.kv_position = _contig(kv_position, keep).data_ptr()
+    p.query_start_loc = _contig(query_start_loc, keep).data_ptr()
+    p.query_positions = _contig(query_positions, keep).data_ptr()
+    p.kv_metric_buffer_len = _contig(kv_metric_buffer_len, keep).data_ptr()
+    p.alibi_slopes = None if alibi_slopes is None else _contig(alibi_slopes.float(), keep).data_ptr()
+    nbytes = lib.kvc_paged_attention_chunk_workspace_bytes(num_tokens, num_heads)
+    ws = workspace(query.device, nbytes + 256, "attn_chunk")
+    p.workspace, p.workspace_bytes = ws.data_ptr(), nbytes
+    p.q_stride, p.out_stride, p.kv_block_stride = query.stride(0), out.stride(0), key_cache.stride(0)
+    p.scale = float(scale)
+    p.num_seqs, p.num_tokens, p.num_heads, p.num_kv_heads = num_seqs, num_tokens, num_heads, int(num_kv_heads)
+    p.head_size, p.block_size = head_size, int(block_size)
+    p.max_num_blocks_per_seq = bt.shape[-1]
+    p.max_context_len, p.max_query_len = int(max_context_len), int(max_query_len)
+    p.dtype, p.kv_cache_dtype = dtypes[query.dtype], kvds[kv_cache_dtype]
+    p.use_l2 = int(bool(use_l2))
+    p.block_layout = _lib.block_layout_id()
+    with on_device(query.device):
+        _lib.check(lib.kvc_paged_attention_chunk(p, _stream(query)))
+    _written(out, metrics)

@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KVC_MI355X_LIB", os.path.join(_HERE, "libkvc_mi355x.so"))
 
 MAX_INT = 2147483000  # reference vllm/kvcompress/metrics.py:12
-ABI_VERSION = 8       # KVC_ABI_VERSION of include/kvc_mi355x.h: the struct layouts mirrored below
+ABI_VERSION = 9       # KVC_ABI_VERSION of include/kvc_mi355x.h: the struct layouts mirrored below
 
 # KVC_LAYOUT_* of include/kvc_mi355x.h: how the bytes INSIDE a cache block are laid out.  The fork hands the ops
 # views of an opaque [2, NB, bs * hd] tensor (reference vllm/attention/ops/paged_attn.py:262-284); the three ops that
@@ -111,6 +111,24 @@ class KvcAttentionParams(ctypes.Structure):
         ("harvest_num_protected", c_void_p), ("harvest_num_seqs", c_int32), ("harvest_layer", c_int32),
         ("harvest_num_layers", c_int32), ("harvest_num_sinks", c_int32),
         ("block_layout", c_int32),
+    ]
+
+
+class KvcAttentionChunkParams(ctypes.Structure):
+    """mirror of ``kvc_attention_chunk_params`` (include/kvc_mi355x.h)"""
+    _fields_ = [
+        ("out", c_void_p), ("metrics", c_void_p),
+        ("query", c_void_p), ("key_cache", c_void_p), ("value_cache", c_void_p),
+        ("block_tables", c_void_p), ("context_lens", c_void_p), ("kv_position", c_void_p),
+        ("query_start_loc", c_void_p), ("query_positions", c_void_p), ("kv_metric_buffer_len", c_void_p),
+        ("alibi_slopes", c_void_p),
+        ("workspace", c_void_p), ("workspace_bytes", c_size_t),
+        ("q_stride", c_int64), ("out_stride", c_int64), ("kv_block_stride", c_int64),
+        ("scale", c_float),
+        ("num_seqs", c_int32), ("num_tokens", c_int32), ("num_heads", c_int32), ("num_kv_heads", c_int32),
+        ("head_size", c_int32), ("block_size", c_int32),
+        ("max_num_blocks_per_seq", c_int32), ("max_context_len", c_int32), ("max_query_len", c_int32),
+        ("dtype", c_int32), ("kv_cache_dtype", c_int32), ("use_l2", c_int32), ("block_layout", c_int32),
     ]
 
 
@@ -214,6 +232,8 @@ SYMBOLS = {
     "kvc_paged_attention_decode_uses_partitions_in": (c_int32, [c_int32, c_int32, c_int32, c_int32, c_int32,
                                                                 c_int32, c_int32]),
     "kvc_paged_attention_decode": (c_int32, [ctypes.POINTER(KvcAttentionParams), c_void_p]),
+    "kvc_paged_attention_chunk_workspace_bytes": (c_size_t, [c_int32, c_int32]),
+    "kvc_paged_attention_chunk": (c_int32, [ctypes.POINTER(KvcAttentionChunkParams), c_void_p]),
 }
 
 _lib = None
@@ -237,7 +257,7 @@ def load() -> ctypes.CDLL:
         fn = getattr(lib, name)          # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args
-    # kvc_schedule_params / kvc_attention_params are mirrored field by field above: a library of another ABI version
+    # kvc_schedule_params / kvc_attention_params / kvc_attention_chunk_params are mirrored field by field above: a library of another ABI version
     # (an old build picked up through KVC_MI355X_LIB) would read pointers at the wrong offsets
     if lib.kvc_abi_version() != ABI_VERSION:
         raise ImportError(f"{LIB_PATH} has ABI version {lib.kvc_abi_version()}, this package mirrors version "

@@ -76,6 +76,12 @@ _ATTN_SCHEMAS = {
         "Tensor kv_metric_buffer_len, int block_size, int max_context_len, "
         "Tensor? alibi_slopes, str kv_cache_dtype, float k_scale, float v_scale, "
         "bool record_kv_metrics) -> ()",
+    # not in the fork: a block of new tokens per sequence over the per-head cache (F5, include/kvc_mi355x.h)
+    "kvcompress_paged_attention_chunk":
+        "(Tensor(a!) out, Tensor query, Tensor key_cache, Tensor value_cache, int num_kv_heads, "
+        "float scale, Tensor block_tables, Tensor context_lens, Tensor kv_position, "
+        "Tensor query_start_loc, Tensor query_positions, Tensor kv_metric_buffer_len, int block_size, "
+        "int max_context_len, int max_query_len, Tensor(b!)? metrics=None, bool use_l2=True) -> ()",
 }
 
 
@@ -125,7 +131,7 @@ COMPILED_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libkvc_
 
 def register(binding: str = "auto") -> str:
     """Make ``torch.ops._C_kvc_ops.*``, ``torch.ops._C_cache_ops.kvcompress_reshape_and_cache`` and
-    ``torch.ops._C.kvcompress_paged_attention_v1/_v2`` resolve to the MI355X kernels.
+    ``torch.ops._C.kvcompress_paged_attention_v1/_v2/_chunk`` resolve to the MI355X kernels.
 
     ``binding``: "compiled" = load ``libkvc_torch.so`` (csrc/kvc_torch_binding.cpp: C++ kernels
     registered with TORCH_LIBRARY_IMPL, no Python frame between the dispatcher and the C ABI);
@@ -158,6 +164,7 @@ def register(binding: str = "auto") -> str:
     _bind("_C", _ATTN_SCHEMAS, {
         "kvcompress_paged_attention_v1": ops.paged_attention_kvc_v1,
         "kvcompress_paged_attention_v2": ops.paged_attention_kvc_v2,
+        "kvcompress_paged_attention_chunk": ops.paged_attention_kvc_chunk,
     })
     _REGISTERED = "python"
     return _REGISTERED
