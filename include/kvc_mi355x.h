@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 9
+#define KVC_ABI_VERSION 10
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -810,7 +810,7 @@ int32_t kvc_paged_attention_decode_uses_partitions_in(int32_t num_seqs, int32_t 
  *   decode steps with fused_metrics would have added.  One writer per slot, a sum formed in a fixed order, no
  *   atomics: identical from run to run.  Slots no token reaches, and all other blocks, are not written.
  * dtype 0 = fp16, 1 = bf16 (query, out and the cache).  KVC_ERR_INVALID, nothing launched: fp8 caches
- * (kv_cache_dtype != 0), alibi_slopes != NULL, head_size other than 64 / 128, block_size other than 16 / 32,
+ * (kv_cache_dtype != 0: they have the entry of their own below), alibi_slopes != NULL, head_size other than 64 / 128, block_size other than 16 / 32,
  * num_heads % num_kv_heads != 0, query rows that are not 16-byte aligned (out rows: 8-byte).  Any
  * num_heads / num_kv_heads >= 1.  Grids are sized from max_query_len and max_context_len (nothing is read back);
  * tokens past max_query_len and slots past max_context_len are ignored.  num_seqs = 0 / no tokens: no-op.
@@ -832,7 +832,7 @@ typedef struct kvc_attention_chunk_params {
   void* workspace;
   size_t workspace_bytes;
   int64_t q_stride, out_stride;         /* elements between tokens */
-  int64_t kv_block_stride;              /* elements between blocks of the caches */
+  int64_t kv_block_stride;              /* elements between blocks of the caches (fp8 caches: bytes) */
   float scale;
   int32_t num_seqs, num_tokens, num_heads, num_kv_heads, head_size, block_size;
   int32_t max_num_blocks_per_seq, max_context_len, max_query_len;
@@ -843,6 +843,26 @@ typedef struct kvc_attention_chunk_params {
 
 size_t kvc_paged_attention_chunk_workspace_bytes(int32_t num_tokens, int32_t num_heads);
 int kvc_paged_attention_chunk(const kvc_attention_chunk_params* p, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * F5 over an fp8 cache (ABI version 10): the op above for kv_cache_dtype 1 (OCP e4m3fn bytes) or 2 (e5m2 bytes),
+ * the pair of the entry above as kvc_reshape_and_cache_fp8 is the pair of kvc_reshape_and_cache.  Blocks as the
+ * fp8 cache write and the decode op define them -- KVC_LAYOUT_REFERENCE: K [head_size/16][block_size][16],
+ * V [head_size][block_size]; KVC_LAYOUT_SLOT_MAJOR: K and V [block_size][head_size] -- and kv_block_stride in BYTES.
+ * Dequantisation rule: every fp8 value converts exactly to fp16 and to bf16, and the two scales are applied in
+ * fp32, not per element:
+ *   logits = scale * k_scale * (query . k8)          out = v_scale * (sum p . v8) / sum p
+ * The decode op (kvc_attention_params with kv_cache_dtype != 0) instead rounds dtype(float(fp8) * scale) for every
+ * element it loads; the two agree exactly for scales that are powers of two (short of overflow) and to within
+ * that rounding otherwise.  Everything else is F5's text above: visibility rule, plain softmax, a row that sees
+ * nothing is 0, every output element is written, the metric rule with its single fixed-order add per slot, the
+ * workspace (same _workspace_bytes companion) and the limits.
+ * KVC_ERR_INVALID, nothing launched: kv_cache_dtype 0 (that cache goes to the entry above) or other than 1 / 2,
+ * a scale that is not finite and > 0, caches that are not 16-byte aligned or kv_block_stride % 16 != 0, and every
+ * refusal of the entry above (alibi_slopes != NULL, head_size other than 64 / 128, block_size other than 16 / 32 ...).
+ * --------------------------------------------------------------------------------- */
+int kvc_paged_attention_chunk_fp8(const kvc_attention_chunk_params* p, float k_scale, float v_scale,
+                                  kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -5,7 +5,11 @@ package can produce the same result: nq successive calls of the decode op with t
 Llama-3-8B heads (32 query / 8 KV, head size 128, block size 16), batch 16, contexts 4k and 32k, nq 16 / 64 / 256,
 with and without the metric, in both block layouts.  Times are medians of device-event timings after warm-up; the
 algorithmic traffic of the chunk op is 2 * hd * e bytes per visible slot and query tile (16 tokens), reported as a
-fraction of 8 TB/s.  Run on the GPU box:  python tools/bench_attention_chunk.py [--json out.json] [--only ctx,nq]"""
+fraction of 8 TB/s.  Run on the GPU box:  python tools/bench_attention_chunk.py [--json out.json] [--only ctx,nq]
+
+--kv-cache-dtype fp8_e4m3 / fp8_e5m2: the same over an fp8 cache (1 byte per element, unit scales -- the decode op's
+fastest fp8 path).  The decode baseline then reads the fp8 cache too, and the chunk op over a 2-byte cache of the same
+geometry is timed in the same process, its launches alternating with the fp8 ones (chunk_auto_ms)."""
 import argparse
 import json
 import os
@@ -37,22 +41,47 @@ def timed(fn, warmup, reps):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def make_cache(ctx, dev, gen):
+def timed_alternating(fa, fb, warmup, reps):
+    """fa and fb launch by launch in turn (what else runs on the machine hits both alike) -> two (median, min, max)"""
+    for _ in range(warmup):
+        fa()
+        fb()
+    torch.cuda.synchronize()
+    ms = ([], [])
+    for _ in range(reps):
+        for fn, acc in ((fa, ms[0]), (fb, ms[1])):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            fn()
+            b.record()
+            b.synchronize()
+            acc.append(a.elapsed_time(b))
+    return tuple((statistics.median(m), min(m), max(m)) for m in ms)
+
+
+def make_cache(ctx, dev, gen, kvd="auto"):
     nblk = (ctx + BS - 1) // BS
     NB = S * HKV * nblk
     kc = torch.randn((NB, HD // 8, BS, 8), device=dev, generator=gen, dtype=torch.float16)
     vc = torch.randn((NB, HD, BS), device=dev, generator=gen, dtype=torch.float16)
+    kc8 = vc8 = None
+    if kvd != "auto":                  # N(0, 1) through the saturating cast: no NaN / inf byte; K [NB, hd/16, bs, 16]
+        tf8 = torch.float8_e5m2 if kvd == "fp8_e5m2" else torch.float8_e4m3fn
+        kc8 = kc.view(NB, HD // 16, BS, 16).to(tf8).view(torch.uint8)
+        vc8 = vc.to(tf8).view(torch.uint8)
     bt = torch.randperm(NB, device=dev, generator=gen).to(torch.int32).view(S, HKV, nblk)
     lens = torch.full((S, HKV), ctx, dtype=torch.int32, device=dev)
     # positions: slot i of every head holds token i (an uncompressed history: every slot inside the window)
     pos = torch.zeros((NB, BS), dtype=torch.int32, device=dev)
     pos[bt.long().view(-1)] = torch.arange(nblk * BS, dtype=torch.int32, device=dev).view(1, nblk, BS).expand(
         S * HKV, nblk, BS).reshape(-1, BS)
-    return kc, vc, bt, lens, pos
+    return kc, vc, bt, lens, pos, kc8, vc8
 
 
-def run(ctx, nq, with_metric, state, dev, gen):
-    kc, vc, bt, lens, pos = state
+def run(ctx, nq, with_metric, state, dev, gen, kvd="auto"):
+    kc, vc, bt, lens, pos, kc8, vc8 = state
+    fp8 = kvd != "auto"
+    dkc, dvc = (kc8, vc8) if fp8 else (kc, vc)          # what the decode baseline reads
     T = S * nq
     q = torch.randn((T, HQ, HD), device=dev, generator=gen, dtype=torch.float16)
     out = torch.empty_like(q)
@@ -66,6 +95,10 @@ def run(ctx, nq, with_metric, state, dev, gen):
         ops.paged_attention_kvc_chunk(out, q, kc, vc, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
                                       metrics=metrics, use_l2=True)
 
+    def chunk_fp8():
+        ops.paged_attention_kvc_chunk(out, q, kc8, vc8, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
+                                      metrics=metrics, use_l2=True, kv_cache_dtype=kvd, k_scale=1.0, v_scale=1.0)
+
     # the decode baseline: step j sees context_lens - (nq - 1 - j) slots and has one query per sequence
     q4, out_d = q.view(S, nq, HQ, HD), torch.empty((S, HQ, HD), dtype=q.dtype, device=dev)
     step_lens = [(lens - (nq - 1 - j)).contiguous() for j in range(nq)]
@@ -75,27 +108,35 @@ def run(ctx, nq, with_metric, state, dev, gen):
     def decode():
         for j in range(nq):
             if with_metric:
-                ops.paged_attention_kvc_fused_metrics(out_d, metrics, q4[:, j], kc, vc, HKV, scale, bt, step_lens[j], pos,
-                                                      step_last[j], buf, BS, ctx, None, "auto", 1.0, 1.0, use_l2=True,
+                ops.paged_attention_kvc_fused_metrics(out_d, metrics, q4[:, j], dkc, dvc, HKV, scale, bt, step_lens[j], pos,
+                                                      step_last[j], buf, BS, ctx, None, kvd, 1.0, 1.0, use_l2=True,
                                                       temp_metrics=temp)
             else:
-                ops.paged_attention_kvc_v1(out_d, temp, q4[:, j], kc, vc, HKV, scale, bt, step_lens[j], pos,
-                                           step_last[j], buf, BS, ctx, None, "auto", 1.0, 1.0, False)
+                ops.paged_attention_kvc_v1(out_d, temp, q4[:, j], dkc, dvc, HKV, scale, bt, step_lens[j], pos,
+                                           step_last[j], buf, BS, ctx, None, kvd, 1.0, 1.0, False)
 
-    c_ms, c_lo, c_hi = timed(chunk, 3, 20)
+    extra = {}
+    if fp8:
+        (c_ms, c_lo, c_hi), (a_ms, a_lo, a_hi) = timed_alternating(chunk_fp8, chunk, 3, 20)
+        extra = dict(kv_cache_dtype=kvd, chunk_auto_ms=a_ms, chunk_auto_ms_min=a_lo, chunk_auto_ms_max=a_hi,
+                     fp8_over_auto=c_ms / a_ms)
+    else:
+        c_ms, c_lo, c_hi = timed(chunk, 3, 20)
     d_ms, d_lo, d_hi = timed(decode, 1, 5)
     tiles = (nq + TILE - 1) // TILE
     visible = sum(max(0, ctx - (nq - 1 - min(nq, TILE * (t + 1)) + 1)) for t in range(tiles))    # per head
-    byts = S * HKV * visible * 2 * HD * 2
+    byts = S * HKV * visible * 2 * HD * (1 if fp8 else 2)
     return dict(layout=kvc.block_layout(), batch=S, ctx=ctx, nq=nq, metrics=with_metric, chunk_ms=c_ms, chunk_ms_min=c_lo,
                 chunk_ms_max=c_hi, decode_x_nq_ms=d_ms, decode_x_nq_ms_min=d_lo, decode_x_nq_ms_max=d_hi,
-                speedup=d_ms / c_ms, chunk_algorithmic_bytes=byts, chunk_fraction_of_8TBps=byts / (c_ms * 1e-3) / PEAK)
+                speedup=d_ms / c_ms, chunk_algorithmic_bytes=byts, chunk_fraction_of_8TBps=byts / (c_ms * 1e-3) / PEAK,
+                **extra)
 
 
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default=None, help="ctx,nq: a single configuration")
+    ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8_e4m3", "fp8_e5m2"))
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_attention_chunk: needs a GPU (nothing is estimated)")
@@ -107,12 +148,12 @@ def main():
         cfgs = [tuple(int(v) for v in args.only.split(","))]
     res = []
     for ctx in sorted({c for c, _ in cfgs}):
-        state = make_cache(ctx, dev, gen)
+        state = make_cache(ctx, dev, gen, args.kv_cache_dtype)
         for layout in ("reference", "slot_major"):
             kvc.set_block_layout(layout)          # (random values: the same buffers serve either layout)
             for nq in [n for c, n in cfgs if c == ctx]:
                 for with_metric in (False, True):
-                    r = run(ctx, nq, with_metric, state, dev, gen)
+                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype)
                     res.append(r)
                     print(json.dumps(r), flush=True)
         del state

@@ -684,7 +684,8 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
                               block_tables, context_lens, kv_position, query_start_loc, query_positions,
                               kv_metric_buffer_len, block_size: int, max_context_len: int,
                               max_query_len: int, metrics: Optional[torch.Tensor] = None,
-                              use_l2: bool = True, alibi_slopes=None, kv_cache_dtype: str = "auto") -> None:
+                              use_l2: bool = True, alibi_slopes=None, kv_cache_dtype: str = "auto",
+                              k_scale: float = 1.0, v_scale: float = 1.0) -> None:
     """Attention of ``nq_s >= 0`` new tokens per sequence over the per-head paged cache (chunked prefill, a
     follow-up turn on a kept cache, prefix reuse, verifying draft tokens): ``query`` / ``out``
     ``[num_tokens, num_heads, head_size]`` packed over the sequences, sequence ``s`` owning tokens
@@ -694,9 +695,21 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     With ``metrics [num_blocks, block_size]``: ``+= sum p^2`` (``use_l2``) or ``sum p`` per slot over the KV
     head's query heads and the tokens ``t`` that see the slot with ``kv_position[slot] <= query_positions[t] -
     kv_metric_buffer_len[s]`` -- what ``nq_s`` calls of ``paged_attention_kvc_fused_metrics`` would have added,
-    formed in a fixed order (identical from run to run).  ``alibi_slopes`` and fp8 caches are refused
-    (include/kvc_mi355x.h, F5)."""
+    formed in a fixed order (identical from run to run).  ``alibi_slopes`` are refused (include/kvc_mi355x.h, F5).
+
+    ``kv_cache_dtype`` ``"fp8"`` / ``"fp8_e4m3"`` / ``"fp8_e5m2"``: 1-byte caches as ``reshape_and_cache_kvc`` writes
+    them (reference blocks K ``[hd/16][bs][16]``, V ``[hd][bs]``; slot-major ``[bs][hd]`` both).  Every fp8 value
+    converts exactly to the query's dtype and the scales are applied in fp32 -- ``logits = scale * k_scale * (q . k8)``,
+    ``out = v_scale * (sum p . v8) / sum p`` -- unlike the decode ops, which round ``dtype(float(fp8) * scale)`` per
+    element.  With ``"auto"`` the scales must be 1."""
     lib = _lib.load()
+    kvds = {"auto": 0, "fp8": 1, "fp8_e4m3": 1, "fp8_e5m2": 2}
+    if kv_cache_dtype not in kvds:
+        raise RuntimeError(f"Unsupported data type of kv cache: {kv_cache_dtype}")
+    if kv_cache_dtype == "auto" and (float(k_scale) != 1.0 or float(v_scale) != 1.0):
+        raise RuntimeError("paged_attention_kvc_chunk: k_scale / v_scale belong to an fp8 cache (\"auto\": both 1)")
+    if kv_cache_dtype != "auto" and (key_cache.element_size() != 1 or value_cache.element_size() != 1):
+        raise RuntimeError("paged_attention_kvc_chunk: an fp8 cache has 1-byte elements")
     for name, t in (("out", out), ("query", query), ("key_cache", key_cache), ("value_cache", value_cache)):
         _require(t, name)
     if metrics is not None:
@@ -707,9 +720,6 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
                     ("kv_position", kv_position), ("query_start_loc", query_start_loc),
                     ("query_positions", query_positions), ("kv_metric_buffer_len", kv_metric_buffer_len)):
         _require(t, name, torch.int32)
-    kvds = {"auto": 0, "fp8": 1, "fp8_e4m3": 1, "fp8_e5m2": 2}
-    if kv_cache_dtype not in kvds:
-        raise RuntimeError(f"Unsupported data type of kv cache: {kv_cache_dtype}")
     dtypes = {torch.float16: 0, torch.bfloat16: 1}
     if query.dtype not in dtypes:
         raise RuntimeError(f"Unsupported data type: {query.dtype}")
@@ -751,5 +761,8 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     p.use_l2 = int(bool(use_l2))
     p.block_layout = _lib.block_layout_id()
     with on_device(query.device):
-        _lib.check(lib.kvc_paged_attention_chunk(p, _stream(query)))
+        if p.kv_cache_dtype == 0:
+            _lib.check(lib.kvc_paged_attention_chunk(p, _stream(query)))
+        else:
+            _lib.check(lib.kvc_paged_attention_chunk_fp8(p, float(k_scale), float(v_scale), _stream(query)))
     _written(out, metrics)

@@ -523,6 +523,83 @@ void kvcompress_paged_attention_chunk(Tensor& out, const Tensor& query, const Te
   if (with_metrics) written(*metrics);
 }
 
+// F5 over an fp8 cache: the op above with 1-byte caches, the kind of their bytes and the two scales (applied in fp32
+// by the kernels, include/kvc_mi355x.h)
+void kvcompress_paged_attention_chunk_fp8(Tensor& out, const Tensor& query, const Tensor& key_cache,
+                                          const Tensor& value_cache, int64_t num_kv_heads, double scale,
+                                          const Tensor& block_tables, const Tensor& context_lens,
+                                          const Tensor& kv_position, const Tensor& query_start_loc,
+                                          const Tensor& query_positions, const Tensor& kv_metric_buffer_len,
+                                          int64_t block_size, int64_t max_context_len, int64_t max_query_len,
+                                          const std::optional<Tensor>& metrics, bool use_l2, std::string kv_cache_dtype,
+                                          double k_scale, double v_scale) {
+  require(out, "out");
+  require(query, "query");
+  require(key_cache, "key_cache");
+  require(value_cache, "value_cache");
+  const bool with_metrics = metrics.has_value() && metrics->defined();
+  if (with_metrics) {
+    require(*metrics, "metrics", at::kFloat);
+    TORCH_CHECK(metrics->is_contiguous(), "paged_attention_kvc: metrics must be contiguous (updated in place)");
+  }
+  for (auto p : {std::make_pair(&block_tables, "block_tables"), std::make_pair(&context_lens, "context_lens"),
+                 std::make_pair(&kv_position, "kv_position"), std::make_pair(&query_start_loc, "query_start_loc"),
+                 std::make_pair(&query_positions, "query_positions"),
+                 std::make_pair(&kv_metric_buffer_len, "kv_metric_buffer_len")})
+    require(*p.first, p.second, at::kInt);
+  int kvd = 0;
+  if (kv_cache_dtype == "fp8" || kv_cache_dtype == "fp8_e4m3") kvd = 1;
+  else if (kv_cache_dtype == "fp8_e5m2") kvd = 2;
+  else { TORCH_CHECK(false, "Unsupported data type of kv cache: ", kv_cache_dtype); }
+  TORCH_CHECK(key_cache.element_size() == 1 && value_cache.element_size() == 1,
+              "paged_attention_kvc_chunk: an fp8 cache has 1-byte elements");
+  TORCH_CHECK(query.scalar_type() == at::kHalf || query.scalar_type() == at::kBFloat16, "Unsupported data type: ",
+              query.scalar_type());
+  TORCH_CHECK(out.scalar_type() == query.scalar_type(), "paged_attention_kvc: query and output must share a dtype");
+  TORCH_CHECK(query.dim() == 3 && query.stride(1) == query.size(2) && query.stride(2) == 1,
+              "paged_attention_kvc: query must be contiguous in (head, dim)");
+  TORCH_CHECK(out.sizes() == query.sizes() && out.stride(1) == out.size(2) && out.stride(2) == 1,
+              "paged_attention_kvc: out must have the query's shape, contiguous in (head, dim)");
+  const int64_t num_seqs = query_start_loc.numel() - 1;
+  TORCH_CHECK(context_lens.numel() == std::max<int64_t>(num_seqs, 0) * num_kv_heads && query_positions.numel() == query.size(0),
+              "paged_attention_kvc_chunk: context_lens is [num_seqs, num_kv_heads] and query_positions [num_tokens], "
+              "num_seqs = len(query_start_loc) - 1");
+  const Tensor bt = block_tables.contiguous(), ctx = context_lens.contiguous(), pos = kv_position.contiguous(),
+               qsl = query_start_loc.contiguous(), qpos = query_positions.contiguous(),
+               buf = kv_metric_buffer_len.contiguous();
+  kvc_attention_chunk_params p;
+  memset(&p, 0, sizeof(p));
+  p.out = out.data_ptr();
+  p.metrics = with_metrics ? metrics->data_ptr<float>() : nullptr;
+  p.query = query.data_ptr();
+  p.key_cache = key_cache.data_ptr();
+  p.value_cache = value_cache.data_ptr();
+  p.block_tables = bt.data_ptr<int32_t>();
+  p.context_lens = ctx.data_ptr<int32_t>();
+  p.kv_position = pos.data_ptr<int32_t>();
+  p.query_start_loc = qsl.data_ptr<int32_t>();
+  p.query_positions = qpos.data_ptr<int32_t>();
+  p.kv_metric_buffer_len = buf.data_ptr<int32_t>();
+  p.q_stride = query.stride(0);
+  p.out_stride = out.stride(0);
+  p.kv_block_stride = key_cache.stride(0);                          // 1-byte elements: bytes
+  p.scale = (float)scale;
+  p.num_seqs = (int32_t)num_seqs; p.num_tokens = (int32_t)query.size(0);
+  p.num_heads = (int32_t)query.size(1); p.num_kv_heads = (int32_t)num_kv_heads;
+  p.head_size = (int32_t)query.size(2); p.block_size = (int32_t)block_size;
+  p.max_num_blocks_per_seq = (int32_t)bt.size(-1);
+  p.max_context_len = (int32_t)max_context_len; p.max_query_len = (int32_t)max_query_len;
+  p.dtype = query.scalar_type() == at::kHalf ? 0 : 1; p.kv_cache_dtype = kvd; p.use_l2 = use_l2 ? 1 : 0;
+  p.block_layout = g_block_layout.load();
+  c10::DeviceGuard guard(query.device());
+  p.workspace_bytes = kvc_paged_attention_chunk_workspace_bytes(p.num_tokens, p.num_heads);
+  const Tensor scratch = workspace(query, p.workspace_bytes + 256, "attn_chunk");
+  p.workspace = scratch.data_ptr<uint8_t>();
+  check(kvc_paged_attention_chunk_fp8(&p, (float)k_scale, (float)v_scale, current_stream(query)));
+  written(out);
+  if (with_metrics) written(*metrics);
+}
+
 // The V1 scheduler pair (csrc/torch_bindings.cpp:374-394, csrc/kvcompress_eviction_kernels.cu
 // schedule_cache_evictions / truncate_cache_evictions): dead in the reference behind `if False:`
 // (vllm/kvcompress/scheduler.py:285) and mis-registered by its wrapper.  The
@@ -601,6 +678,13 @@ TORCH_LIBRARY_FRAGMENT(_C, m) {
           "int num_kv_heads, float scale, Tensor block_tables, Tensor context_lens, Tensor kv_position, "
           "Tensor query_start_loc, Tensor query_positions, Tensor kv_metric_buffer_len, int block_size, "
           "int max_context_len, int max_query_len, Tensor(b!)? metrics=None, bool use_l2=True) -> ()");
+  // ... and over an fp8 cache
+  if (!has_schema("_C::kvcompress_paged_attention_chunk_fp8"))
+    m.def("kvcompress_paged_attention_chunk_fp8(Tensor(a!) out, Tensor query, Tensor key_cache, Tensor value_cache, "
+          "int num_kv_heads, float scale, Tensor block_tables, Tensor context_lens, Tensor kv_position, "
+          "Tensor query_start_loc, Tensor query_positions, Tensor kv_metric_buffer_len, int block_size, "
+          "int max_context_len, int max_query_len, Tensor(b!)? metrics=None, bool use_l2=True, "
+          "str kv_cache_dtype=\"fp8\", float k_scale=1.0, float v_scale=1.0) -> ()");
 }
 
 // not in the fork: the start-up hooks of this binding
@@ -627,4 +711,5 @@ TORCH_LIBRARY_IMPL(_C, CUDA, m) {
   m.impl("kvcompress_paged_attention_v1", &kvcompress_paged_attention_v1);
   m.impl("kvcompress_paged_attention_v2", &kvcompress_paged_attention_v2);
   m.impl("kvcompress_paged_attention_chunk", &kvcompress_paged_attention_chunk);
+  m.impl("kvcompress_paged_attention_chunk_fp8", &kvcompress_paged_attention_chunk_fp8);
 }

@@ -82,6 +82,13 @@ _ATTN_SCHEMAS = {
         "float scale, Tensor block_tables, Tensor context_lens, Tensor kv_position, "
         "Tensor query_start_loc, Tensor query_positions, Tensor kv_metric_buffer_len, int block_size, "
         "int max_context_len, int max_query_len, Tensor(b!)? metrics=None, bool use_l2=True) -> ()",
+    # ... and over an fp8 cache (scales applied in fp32, include/kvc_mi355x.h)
+    "kvcompress_paged_attention_chunk_fp8":
+        "(Tensor(a!) out, Tensor query, Tensor key_cache, Tensor value_cache, int num_kv_heads, "
+        "float scale, Tensor block_tables, Tensor context_lens, Tensor kv_position, "
+        "Tensor query_start_loc, Tensor query_positions, Tensor kv_metric_buffer_len, int block_size, "
+        "int max_context_len, int max_query_len, Tensor(b!)? metrics=None, bool use_l2=True, "
+        "str kv_cache_dtype=\"fp8\", float k_scale=1.0, float v_scale=1.0) -> ()",
 }
 
 
@@ -104,6 +111,15 @@ def _execute_cache_moves(k, v, m, p, cmi, cmc, offs, blocks_per_head, threads_pe
 
 def _reshape_and_cache(key, value, kc, vc, met, slots, bias, dtype, k_scale, v_scale):
     ops.reshape_and_cache_kvc(key, value, kc, vc, met, slots, bias, dtype, k_scale, v_scale)
+
+
+def _paged_attention_chunk_fp8(out, query, kc, vc, num_kv_heads, scale, bt, ctx, pos, qsl, qpos, buf, block_size,
+                               max_context_len, max_query_len, metrics=None, use_l2=True, kv_cache_dtype="fp8",
+                               k_scale=1.0, v_scale=1.0):
+    if kv_cache_dtype == "auto":
+        raise RuntimeError("kvcompress_paged_attention_chunk_fp8: an \"auto\" cache goes to kvcompress_paged_attention_chunk")
+    ops.paged_attention_kvc_chunk(out, query, kc, vc, num_kv_heads, scale, bt, ctx, pos, qsl, qpos, buf, block_size,
+                                  max_context_len, max_query_len, metrics, use_l2, None, kv_cache_dtype, k_scale, v_scale)
 
 
 def _bind(ns, schemas, impls):
@@ -131,7 +147,7 @@ COMPILED_LIB = os.path.join(os.path.dirname(os.path.abspath(__file__)), "libkvc_
 
 def register(binding: str = "auto") -> str:
     """Make ``torch.ops._C_kvc_ops.*``, ``torch.ops._C_cache_ops.kvcompress_reshape_and_cache`` and
-    ``torch.ops._C.kvcompress_paged_attention_v1/_v2/_chunk`` resolve to the MI355X kernels.
+    ``torch.ops._C.kvcompress_paged_attention_v1/_v2/_chunk/_chunk_fp8`` resolve to the MI355X kernels.
 
     ``binding``: "compiled" = load ``libkvc_torch.so`` (csrc/kvc_torch_binding.cpp: C++ kernels
     registered with TORCH_LIBRARY_IMPL, no Python frame between the dispatcher and the C ABI);
@@ -165,6 +181,7 @@ def register(binding: str = "auto") -> str:
         "kvcompress_paged_attention_v1": ops.paged_attention_kvc_v1,
         "kvcompress_paged_attention_v2": ops.paged_attention_kvc_v2,
         "kvcompress_paged_attention_chunk": ops.paged_attention_kvc_chunk,
+        "kvcompress_paged_attention_chunk_fp8": _paged_attention_chunk_fp8,
     })
     _REGISTERED = "python"
     return _REGISTERED
