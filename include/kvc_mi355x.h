@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 10
+#define KVC_ABI_VERSION 11
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -863,6 +863,38 @@ int kvc_paged_attention_chunk(const kvc_attention_chunk_params* p, kvc_stream_t 
  * --------------------------------------------------------------------------------- */
 int kvc_paged_attention_chunk_fp8(const kvc_attention_chunk_params* p, float k_scale, float v_scale,
                                   kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * F5 for short query blocks (ABI version 11): the "short" schedule of the op above, for calls whose query block is
+ * so short that all (token, query head) pairs of a KV head fit two 16-row MFMA tiles:
+ *   R = max_query_len * (num_heads / num_kv_heads) <= 32
+ * (8 tokens at 4 query heads per KV head, 4 at 8, 32 at 1: verifying draft tokens, a short follow-up turn).  The
+ * entry above gives such a call one workgroup per (sequence, KV head) that walks the whole context alone over a
+ * tile of mostly empty rows; this one splits the KEYS: a workgroup owns one partition of PL slots of one (sequence,
+ * KV head) and all R rows, its four waves share the partition's keys, and a second kernel merges the partitions
+ * of a head in ascending order (not launched when max_context_len <= PL).
+ * Semantics are F5's text above, word for word: visibility rule, plain softmax with fp32 statistics and
+ * accumulation, output rounded once, a row that sees nothing is 0, every output element of every token is written,
+ * the metric rule with its single fixed-order add per slot (the same metric kernel runs behind either schedule).
+ * The two schedules sum in different orders: their outputs agree to rounding, not bit for bit.
+ *   _short_eligible   1 if the call may take this entry (R <= 32, kv_cache_dtype 0, num_heads a multiple of
+ *                     num_kv_heads), else 0.
+ *   _short_partition  PL: a multiple of 128 and a function of max_context_len alone (512, doubled until 32
+ *                     partitions cover max_context_len) -- a call's result does not depend on the batch, and the
+ *                     same call gives the same bits.
+ *   _short_workspace_bytes  size of the partial scratch (16-byte aligned): per sequence, partition and row the
+ *                     unnormalised fp32 output with its max and sum; 0 when max_context_len <= PL.
+ * The entry takes the params struct of F5; workspace is still the row statistics.  KVC_ERR_INVALID, nothing
+ * launched: every refusal of kvc_paged_attention_chunk, an fp8 cache (kv_cache_dtype != 0: it stays on the entry of
+ * its own), more than 32 rows, a partial scratch that is too small or not 16-byte aligned.
+ * --------------------------------------------------------------------------------- */
+int32_t kvc_paged_attention_chunk_short_eligible(int32_t num_heads, int32_t num_kv_heads, int32_t max_query_len,
+                                                 int32_t kv_cache_dtype);
+int32_t kvc_paged_attention_chunk_short_partition(int32_t max_context_len);
+size_t kvc_paged_attention_chunk_short_workspace_bytes(int32_t num_seqs, int32_t num_heads, int32_t head_size,
+                                                       int32_t max_query_len, int32_t max_context_len);
+int kvc_paged_attention_chunk_short(const kvc_attention_chunk_params* p, void* partial, size_t partial_bytes,
+                                    kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

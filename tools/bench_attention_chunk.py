@@ -9,7 +9,12 @@ fraction of 8 TB/s.  Run on the GPU box:  python tools/bench_attention_chunk.py 
 
 --kv-cache-dtype fp8_e4m3 / fp8_e5m2: the same over an fp8 cache (1 byte per element, unit scales -- the decode op's
 fastest fp8 path).  The decode baseline then reads the fp8 cache too, and the chunk op over a 2-byte cache of the same
-geometry is timed in the same process, its launches alternating with the fp8 ones (chunk_auto_ms)."""
+geometry is timed in the same process, its launches alternating with the fp8 ones (chunk_auto_ms).
+
+--nq 1,2,4,8: short query blocks (draft verification).  schedule="short" against schedule="tile", launches alternating
+in one process, and both against decode x nq; batch 16 at contexts 4k and 32k, one line each for batch 1 and batch 64
+at 4k.  The traffic is then counted per CALL (2 * hd * e bytes per visible slot, read once), and the largest
+difference between the two schedules' outputs is recorded next to the times."""
 import argparse
 import json
 import os
@@ -78,7 +83,7 @@ def make_cache(ctx, dev, gen, kvd="auto"):
     return kc, vc, bt, lens, pos, kc8, vc8
 
 
-def run(ctx, nq, with_metric, state, dev, gen, kvd="auto"):
+def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False):
     kc, vc, bt, lens, pos, kc8, vc8 = state
     fp8 = kvd != "auto"
     dkc, dvc = (kc8, vc8) if fp8 else (kc, vc)          # what the decode baseline reads
@@ -91,9 +96,9 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto"):
     metrics = torch.zeros(pos.shape, dtype=torch.float32, device=dev) if with_metric else None
     scale = HD ** -0.5
 
-    def chunk():
+    def chunk(schedule="tile", out=out):
         ops.paged_attention_kvc_chunk(out, q, kc, vc, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
-                                      metrics=metrics, use_l2=True)
+                                      metrics=metrics, use_l2=True, schedule=schedule)
 
     def chunk_fp8():
         ops.paged_attention_kvc_chunk(out, q, kc8, vc8, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
@@ -116,6 +121,19 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto"):
                                            step_last[j], buf, BS, ctx, None, kvd, 1.0, 1.0, False)
 
     extra = {}
+    if short:
+        (s_ms, s_lo, s_hi), (t_ms, t_lo, t_hi) = timed_alternating(lambda: chunk("short"), chunk, 5, 40)
+        d_ms, d_lo, d_hi = timed(decode, 1, 5)
+        o_s, o_t = torch.empty_like(q), torch.empty_like(q)
+        chunk("short", o_s)
+        chunk("tile", o_t)
+        byts = S * HKV * ctx * 2 * HD * 2
+        return dict(layout=kvc.block_layout(), batch=S, ctx=ctx, nq=nq, metrics=with_metric, short_ms=s_ms, short_ms_min=s_lo,
+                    short_ms_max=s_hi, tile_ms=t_ms, tile_ms_min=t_lo, tile_ms_max=t_hi, decode_x_nq_ms=d_ms,
+                    decode_x_nq_ms_min=d_lo, decode_x_nq_ms_max=d_hi, tile_over_short=t_ms / s_ms,
+                    decode_over_short=d_ms / s_ms, call_algorithmic_bytes=byts,
+                    short_fraction_of_8TBps=byts / (s_ms * 1e-3) / PEAK, tile_fraction_of_8TBps=byts / (t_ms * 1e-3) / PEAK,
+                    short_vs_tile_max_abs_diff=float((o_s.float() - o_t.float()).abs().max()), out_tolerance=2e-3)
     if fp8:
         (c_ms, c_lo, c_hi), (a_ms, a_lo, a_hi) = timed_alternating(chunk_fp8, chunk, 3, 20)
         extra = dict(kv_cache_dtype=kvd, chunk_auto_ms=a_ms, chunk_auto_ms_min=a_lo, chunk_auto_ms_max=a_hi,
@@ -137,6 +155,7 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default=None, help="ctx,nq: a single configuration")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8_e4m3", "fp8_e5m2"))
+    ap.add_argument("--nq", default=None, help="short query blocks, e.g. 1,2,4,8: the short schedule against the tile one")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_attention_chunk: needs a GPU (nothing is estimated)")
@@ -144,6 +163,9 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     cfgs = [(c, n) for c in (4096, 32768) for n in (16, 64, 256)]
+    short = args.nq is not None
+    if short:
+        cfgs = [(c, int(n)) for c in (4096, 32768) for n in args.nq.split(",")]
     if args.only:
         cfgs = [tuple(int(v) for v in args.only.split(","))]
     res = []
@@ -153,11 +175,19 @@ def main():
             kvc.set_block_layout(layout)          # (random values: the same buffers serve either layout)
             for nq in [n for c, n in cfgs if c == ctx]:
                 for with_metric in (False, True):
-                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype)
+                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short)
                     res.append(r)
                     print(json.dumps(r), flush=True)
         del state
     kvc.set_block_layout("reference")
+    global S
+    for batch in (1, 64) if short and not args.only else ():
+        S = batch
+        state = make_cache(4096, dev, gen)
+        r = run(4096, 4, False, state, dev, gen, short=True)
+        res.append(r)
+        print(json.dumps(r), flush=True)
+        del state
     if args.json:
         json.dump(res, open(args.json, "w"), indent=1)
 

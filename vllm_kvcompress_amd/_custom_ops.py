@@ -673,11 +673,19 @@ def paged_attention_kvc_v2(out, kv_metric_out, exp_sum, max_logits, tmp_out, tmp
 # ---------------------------------------------------------------------------------------
 # F5: query-block attention over the per-head cache (not in the reference: its prefix-enabled
 # prefill branch, vllm/attention/backends/flash_attn.py:1046-1063, cannot read a per-head cache)
-def reserve_attention_chunk_scratch(device, num_tokens: int, num_heads: int) -> None:
+def reserve_attention_chunk_scratch(device, num_tokens: int, num_heads: int, *, num_seqs: int = 0,
+                                    head_size: int = 0, max_query_len: int = 0, max_context_len: int = 0) -> None:
     """Pre-size the row-statistics scratch of ``paged_attention_kvc_chunk`` for the largest token batch the
-    engine will run, so the op never allocates while serving or inside a HIP-graph capture."""
-    reserve_workspace(torch.device(device), _lib.load().kvc_paged_attention_chunk_workspace_bytes(
+    engine will run, so the op never allocates while serving or inside a HIP-graph capture.  With ``num_seqs`` /
+    ``head_size`` / ``max_query_len`` / ``max_context_len`` also the partial scratch of the short schedule (the
+    per-partition results of calls with at most 32 (token, query head) rows per KV head) for the largest such call."""
+    lib = _lib.load()
+    reserve_workspace(torch.device(device), lib.kvc_paged_attention_chunk_workspace_bytes(
         int(num_tokens), int(num_heads)) + 256, "attn_chunk")
+    if num_seqs > 0 and head_size > 0 and max_query_len > 0 and max_context_len > 0:
+        reserve_workspace(torch.device(device), lib.kvc_paged_attention_chunk_short_workspace_bytes(
+            int(num_seqs), int(num_heads), int(head_size), int(max_query_len), int(max_context_len)) + 256,
+            "attn_chunk_short")
 
 
 def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: int, scale: float,
@@ -685,7 +693,7 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
                               kv_metric_buffer_len, block_size: int, max_context_len: int,
                               max_query_len: int, metrics: Optional[torch.Tensor] = None,
                               use_l2: bool = True, alibi_slopes=None, kv_cache_dtype: str = "auto",
-                              k_scale: float = 1.0, v_scale: float = 1.0) -> None:
+                              k_scale: float = 1.0, v_scale: float = 1.0, schedule: str = "auto") -> None:
     """Attention of ``nq_s >= 0`` new tokens per sequence over the per-head paged cache (chunked prefill, a
     follow-up turn on a kept cache, prefix reuse, verifying draft tokens): ``query`` / ``out``
     ``[num_tokens, num_heads, head_size]`` packed over the sequences, sequence ``s`` owning tokens
@@ -701,8 +709,17 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     them (reference blocks K ``[hd/16][bs][16]``, V ``[hd][bs]``; slot-major ``[bs][hd]`` both).  Every fp8 value
     converts exactly to the query's dtype and the scales are applied in fp32 -- ``logits = scale * k_scale * (q . k8)``,
     ``out = v_scale * (sum p . v8) / sum p`` -- unlike the decode ops, which round ``dtype(float(fp8) * scale)`` per
-    element.  With ``"auto"`` the scales must be 1."""
+    element.  With ``"auto"`` the scales must be 1.
+
+    ``schedule``: ``"tile"`` -- a workgroup owns 16 query tokens of a (sequence, KV head) and walks the whole context;
+    ``"short"`` -- for ``max_query_len * (num_heads / num_kv_heads) <= 32`` (verifying a few draft tokens, a short
+    follow-up turn) the keys are split over workgroups and waves and a second kernel merges the partitions
+    (``kvc_paged_attention_chunk_short``, include/kvc_mi355x.h; a call that is not eligible raises); ``"auto"``
+    takes the short schedule exactly when the call is eligible and the cache is not fp8.  Same semantics either
+    way; the two sum in different orders, so their outputs agree to rounding."""
     lib = _lib.load()
+    if schedule not in ("auto", "tile", "short"):
+        raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r}: expected \"auto\", \"tile\" or \"short\"")
     kvds = {"auto": 0, "fp8": 1, "fp8_e4m3": 1, "fp8_e5m2": 2}
     if kv_cache_dtype not in kvds:
         raise RuntimeError(f"Unsupported data type of kv cache: {kv_cache_dtype}")
@@ -760,8 +777,15 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     p.dtype, p.kv_cache_dtype = dtypes[query.dtype], kvds[kv_cache_dtype]
     p.use_l2 = int(bool(use_l2))
     p.block_layout = _lib.block_layout_id()
+    short = schedule == "short" or (schedule == "auto" and bool(lib.kvc_paged_attention_chunk_short_eligible(
+        p.num_heads, p.num_kv_heads, p.max_query_len, p.kv_cache_dtype)))
     with on_device(query.device):
-        if p.kv_cache_dtype == 0:
+        if short:
+            pbytes = lib.kvc_paged_attention_chunk_short_workspace_bytes(num_seqs, num_heads, head_size,
+                                                                         p.max_query_len, p.max_context_len)
+            part = workspace(query.device, pbytes + 256, "attn_chunk_short")
+            _lib.check(lib.kvc_paged_attention_chunk_short(p, part.data_ptr(), pbytes, _stream(query)))
+        elif p.kv_cache_dtype == 0:
             _lib.check(lib.kvc_paged_attention_chunk(p, _stream(query)))
         else:
             _lib.check(lib.kvc_paged_attention_chunk_fp8(p, float(k_scale), float(v_scale), _stream(query)))

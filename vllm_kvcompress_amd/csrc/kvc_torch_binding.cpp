@@ -518,7 +518,15 @@ void kvcompress_paged_attention_chunk(Tensor& out, const Tensor& query, const Te
   p.workspace_bytes = kvc_paged_attention_chunk_workspace_bytes(p.num_tokens, p.num_heads);
   const Tensor scratch = workspace(query, p.workspace_bytes + 256, "attn_chunk");
   p.workspace = scratch.data_ptr<uint8_t>();
-  check(kvc_paged_attention_chunk(&p, current_stream(query)));
+  // the schedule: the library's own rule, as vllm_kvcompress_amd._custom_ops applies it with schedule="auto"
+  if (kvc_paged_attention_chunk_short_eligible(p.num_heads, p.num_kv_heads, p.max_query_len, p.kv_cache_dtype)) {
+    const size_t pbytes = kvc_paged_attention_chunk_short_workspace_bytes(p.num_seqs, p.num_heads, p.head_size,
+                                                                          p.max_query_len, p.max_context_len);
+    const Tensor partial = workspace(query, pbytes + 256, "attn_chunk_short");
+    check(kvc_paged_attention_chunk_short(&p, partial.data_ptr<uint8_t>(), pbytes, current_stream(query)));
+  } else {
+    check(kvc_paged_attention_chunk(&p, current_stream(query)));
+  }
   written(out);
   if (with_metrics) written(*metrics);
 }
