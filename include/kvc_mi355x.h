@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 11
+#define KVC_ABI_VERSION 12
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -885,8 +885,9 @@ int kvc_paged_attention_chunk_fp8(const kvc_attention_chunk_params* p, float k_s
  *   _short_workspace_bytes  size of the partial scratch (16-byte aligned): per sequence, partition and row the
  *                     unnormalised fp32 output with its max and sum; 0 when max_context_len <= PL.
  * The entry takes the params struct of F5; workspace is still the row statistics.  KVC_ERR_INVALID, nothing
- * launched: every refusal of kvc_paged_attention_chunk, an fp8 cache (kv_cache_dtype != 0: it stays on the entry of
- * its own), more than 32 rows, a partial scratch that is too small or not 16-byte aligned.
+ * launched: every refusal of kvc_paged_attention_chunk, an fp8 cache (kv_cache_dtype != 0: it goes to
+ * kvc_paged_attention_chunk_short_fp8 below), more than 32 rows, a partial scratch that is too small or not 16-byte
+ * aligned.
  * --------------------------------------------------------------------------------- */
 int32_t kvc_paged_attention_chunk_short_eligible(int32_t num_heads, int32_t num_kv_heads, int32_t max_query_len,
                                                  int32_t kv_cache_dtype);
@@ -895,6 +896,26 @@ size_t kvc_paged_attention_chunk_short_workspace_bytes(int32_t num_seqs, int32_t
                                                        int32_t max_query_len, int32_t max_context_len);
 int kvc_paged_attention_chunk_short(const kvc_attention_chunk_params* p, void* partial, size_t partial_bytes,
                                     kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * The short schedule over an fp8 cache (ABI version 12): kvc_paged_attention_chunk_short for kv_cache_dtype 1 (OCP
+ * e4m3fn bytes) or 2 (e5m2 bytes), in both block layouts.  Blocks, kv_block_stride in BYTES and the dequantisation
+ * rule are those of kvc_paged_attention_chunk_fp8 -- bytes convert exactly to the query's dtype, logits = scale *
+ * k_scale * (query . k8), out = v_scale * (sum p . v8) / sum p, the row statistics without v_scale --; schedule,
+ * partition length, partial scratch (the _short_partition and _short_workspace_bytes companions above: they do not
+ * depend on the cache type) and semantics are those of the short entry above.
+ *   _short_fp8_eligible  1 if the call may take this entry (R <= 32, kv_cache_dtype 1 or 2, num_heads a multiple of
+ *                        num_kv_heads), else 0.  Measured the short schedule beat the tile schedule
+ *                        over fp8 caches in every row, so callers that choose for themselves take it whenever eligible.
+ * KVC_ERR_INVALID, nothing launched: every refusal of kvc_paged_attention_chunk_fp8 (kv_cache_dtype 0 -- that cache
+ * goes to kvc_paged_attention_chunk_short --, a scale that is not finite and > 0, ALiBi slopes, head and block sizes,
+ * 16-byte alignment) and of the short entry (more than 32 rows, a partial scratch that is too small or not 16-byte
+ * aligned).
+ * --------------------------------------------------------------------------------- */
+int32_t kvc_paged_attention_chunk_short_fp8_eligible(int32_t num_heads, int32_t num_kv_heads, int32_t max_query_len,
+                                                     int32_t kv_cache_dtype);
+int kvc_paged_attention_chunk_short_fp8(const kvc_attention_chunk_params* p, float k_scale, float v_scale, void* partial,
+                                        size_t partial_bytes, kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -14,7 +14,9 @@ geometry is timed in the same process, its launches alternating with the fp8 one
 --nq 1,2,4,8: short query blocks (draft verification).  schedule="short" against schedule="tile", launches alternating
 in one process, and both against decode x nq; batch 16 at contexts 4k and 32k, one line each for batch 1 and batch 64
 at 4k.  The traffic is then counted per CALL (2 * hd * e bytes per visible slot, read once), and the largest
-difference between the two schedules' outputs is recorded next to the times."""
+difference between the two schedules' outputs is recorded next to the times.  With --kv-cache-dtype fp8_*: the two
+schedules and the decode calls read the fp8 cache, and a third alternating leg times the short schedule over the
+2-byte cache of the same geometry (short_auto_ms; fp8_short_over_auto_short is the ratio of the two medians)."""
 import argparse
 import json
 import os
@@ -46,15 +48,15 @@ def timed(fn, warmup, reps):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def timed_alternating(fa, fb, warmup, reps):
-    """fa and fb launch by launch in turn (what else runs on the machine hits both alike) -> two (median, min, max)"""
+def timed_alternating(*fns, warmup, reps):
+    """the given calls launch by launch in turn (what else runs on the machine hits all alike) -> a (median, min, max) each"""
     for _ in range(warmup):
-        fa()
-        fb()
+        for fn in fns:
+            fn()
     torch.cuda.synchronize()
-    ms = ([], [])
+    ms = tuple([] for _ in fns)
     for _ in range(reps):
-        for fn, acc in ((fa, ms[0]), (fb, ms[1])):
+        for fn, acc in zip(fns, ms):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
             fn()
@@ -100,9 +102,10 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False):
         ops.paged_attention_kvc_chunk(out, q, kc, vc, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
                                       metrics=metrics, use_l2=True, schedule=schedule)
 
-    def chunk_fp8():
+    def chunk_fp8(schedule="tile", out=out):
         ops.paged_attention_kvc_chunk(out, q, kc8, vc8, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
-                                      metrics=metrics, use_l2=True, kv_cache_dtype=kvd, k_scale=1.0, v_scale=1.0)
+                                      metrics=metrics, use_l2=True, kv_cache_dtype=kvd, k_scale=1.0, v_scale=1.0,
+                                      schedule=schedule)
 
     # the decode baseline: step j sees context_lens - (nq - 1 - j) slots and has one query per sequence
     q4, out_d = q.view(S, nq, HQ, HD), torch.empty((S, HQ, HD), dtype=q.dtype, device=dev)
@@ -122,20 +125,27 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False):
 
     extra = {}
     if short:
-        (s_ms, s_lo, s_hi), (t_ms, t_lo, t_hi) = timed_alternating(lambda: chunk("short"), chunk, 5, 40)
+        # fp8: short and tile over the fp8 cache, and the short schedule over the 2-byte cache of the same geometry
+        sched = chunk_fp8 if fp8 else chunk
+        fns = [lambda: sched("short"), lambda: sched("tile")] + ([lambda: chunk("short")] if fp8 else [])
+        (s_ms, s_lo, s_hi), (t_ms, t_lo, t_hi), *rest = timed_alternating(*fns, warmup=5, reps=40)
         d_ms, d_lo, d_hi = timed(decode, 1, 5)
         o_s, o_t = torch.empty_like(q), torch.empty_like(q)
-        chunk("short", o_s)
-        chunk("tile", o_t)
-        byts = S * HKV * ctx * 2 * HD * 2
+        sched("short", o_s)
+        sched("tile", o_t)
+        byts = S * HKV * ctx * 2 * HD * (1 if fp8 else 2)
+        if fp8:
+            (a_ms, a_lo, a_hi), = rest
+            extra = dict(kv_cache_dtype=kvd, short_auto_ms=a_ms, short_auto_ms_min=a_lo, short_auto_ms_max=a_hi,
+                         fp8_short_over_auto_short=s_ms / a_ms)
         return dict(layout=kvc.block_layout(), batch=S, ctx=ctx, nq=nq, metrics=with_metric, short_ms=s_ms, short_ms_min=s_lo,
                     short_ms_max=s_hi, tile_ms=t_ms, tile_ms_min=t_lo, tile_ms_max=t_hi, decode_x_nq_ms=d_ms,
                     decode_x_nq_ms_min=d_lo, decode_x_nq_ms_max=d_hi, tile_over_short=t_ms / s_ms,
                     decode_over_short=d_ms / s_ms, call_algorithmic_bytes=byts,
                     short_fraction_of_8TBps=byts / (s_ms * 1e-3) / PEAK, tile_fraction_of_8TBps=byts / (t_ms * 1e-3) / PEAK,
-                    short_vs_tile_max_abs_diff=float((o_s.float() - o_t.float()).abs().max()), out_tolerance=2e-3)
+                    short_vs_tile_max_abs_diff=float((o_s.float() - o_t.float()).abs().max()), out_tolerance=2e-3, **extra)
     if fp8:
-        (c_ms, c_lo, c_hi), (a_ms, a_lo, a_hi) = timed_alternating(chunk_fp8, chunk, 3, 20)
+        (c_ms, c_lo, c_hi), (a_ms, a_lo, a_hi) = timed_alternating(chunk_fp8, chunk, warmup=3, reps=20)
         extra = dict(kv_cache_dtype=kvd, chunk_auto_ms=a_ms, chunk_auto_ms_min=a_lo, chunk_auto_ms_max=a_hi,
                      fp8_over_auto=c_ms / a_ms)
     else:
@@ -183,8 +193,8 @@ def main():
     global S
     for batch in (1, 64) if short and not args.only else ():
         S = batch
-        state = make_cache(4096, dev, gen)
-        r = run(4096, 4, False, state, dev, gen, short=True)
+        state = make_cache(4096, dev, gen, args.kv_cache_dtype)
+        r = run(4096, 4, False, state, dev, gen, args.kv_cache_dtype, short=True)
         res.append(r)
         print(json.dumps(r), flush=True)
         del state

@@ -714,9 +714,10 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     ``schedule``: ``"tile"`` -- a workgroup owns 16 query tokens of a (sequence, KV head) and walks the whole context;
     ``"short"`` -- for ``max_query_len * (num_heads / num_kv_heads) <= 32`` (verifying a few draft tokens, a short
     follow-up turn) the keys are split over workgroups and waves and a second kernel merges the partitions
-    (``kvc_paged_attention_chunk_short``, include/kvc_mi355x.h; a call that is not eligible raises); ``"auto"``
-    takes the short schedule exactly when the call is eligible and the cache is not fp8.  Same semantics either
-    way; the two sum in different orders, so their outputs agree to rounding."""
+    (``kvc_paged_attention_chunk_short``, over an fp8 cache ``kvc_paged_attention_chunk_short_fp8``,
+    include/kvc_mi355x.h; a call that is not eligible raises); ``"auto"`` takes the short schedule exactly when the
+    call is eligible, whatever the cache type.  Same semantics either way; the two sum in different orders, so
+    their outputs agree to rounding."""
     lib = _lib.load()
     if schedule not in ("auto", "tile", "short"):
         raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r}: expected \"auto\", \"tile\" or \"short\"")
@@ -777,14 +778,20 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     p.dtype, p.kv_cache_dtype = dtypes[query.dtype], kvds[kv_cache_dtype]
     p.use_l2 = int(bool(use_l2))
     p.block_layout = _lib.block_layout_id()
-    short = schedule == "short" or (schedule == "auto" and bool(lib.kvc_paged_attention_chunk_short_eligible(
+    eligible = (lib.kvc_paged_attention_chunk_short_eligible if p.kv_cache_dtype == 0
+                else lib.kvc_paged_attention_chunk_short_fp8_eligible)
+    short = schedule == "short" or (schedule == "auto" and bool(eligible(
         p.num_heads, p.num_kv_heads, p.max_query_len, p.kv_cache_dtype)))
     with on_device(query.device):
         if short:
             pbytes = lib.kvc_paged_attention_chunk_short_workspace_bytes(num_seqs, num_heads, head_size,
                                                                          p.max_query_len, p.max_context_len)
             part = workspace(query.device, pbytes + 256, "attn_chunk_short")
-            _lib.check(lib.kvc_paged_attention_chunk_short(p, part.data_ptr(), pbytes, _stream(query)))
+            if p.kv_cache_dtype == 0:
+                _lib.check(lib.kvc_paged_attention_chunk_short(p, part.data_ptr(), pbytes, _stream(query)))
+            else:
+                _lib.check(lib.kvc_paged_attention_chunk_short_fp8(p, float(k_scale), float(v_scale), part.data_ptr(),
+                                                                   pbytes, _stream(query)))
         elif p.kv_cache_dtype == 0:
             _lib.check(lib.kvc_paged_attention_chunk(p, _stream(query)))
         else:

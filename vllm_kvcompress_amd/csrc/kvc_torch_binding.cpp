@@ -603,7 +603,16 @@ void kvcompress_paged_attention_chunk_fp8(Tensor& out, const Tensor& query, cons
   p.workspace_bytes = kvc_paged_attention_chunk_workspace_bytes(p.num_tokens, p.num_heads);
   const Tensor scratch = workspace(query, p.workspace_bytes + 256, "attn_chunk");
   p.workspace = scratch.data_ptr<uint8_t>();
-  check(kvc_paged_attention_chunk_fp8(&p, (float)k_scale, (float)v_scale, current_stream(query)));
+  // the rule of the Python op's schedule="auto": the short schedule whenever the call is eligible
+  if (kvc_paged_attention_chunk_short_fp8_eligible(p.num_heads, p.num_kv_heads, p.max_query_len, p.kv_cache_dtype)) {
+    const size_t pbytes = kvc_paged_attention_chunk_short_workspace_bytes(p.num_seqs, p.num_heads, p.head_size,
+                                                                          p.max_query_len, p.max_context_len);
+    const Tensor partial = workspace(query, pbytes + 256, "attn_chunk_short");
+    check(kvc_paged_attention_chunk_short_fp8(&p, (float)k_scale, (float)v_scale, partial.data_ptr<uint8_t>(), pbytes,
+                                              current_stream(query)));
+  } else {
+    check(kvc_paged_attention_chunk_fp8(&p, (float)k_scale, (float)v_scale, current_stream(query)));
+  }
   written(out);
   if (with_metrics) written(*metrics);
 }
