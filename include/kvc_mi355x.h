@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 12
+#define KVC_ABI_VERSION 13
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -916,6 +916,37 @@ int32_t kvc_paged_attention_chunk_short_fp8_eligible(int32_t num_heads, int32_t 
                                                      int32_t kv_cache_dtype);
 int kvc_paged_attention_chunk_short_fp8(const kvc_attention_chunk_params* p, float k_scale, float v_scale, void* partial,
                                         size_t partial_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * F5 with the keys split over workgroups for query blocks of any length (ABI version 13): the "split" schedule.
+ * The tile schedule (kvc_paged_attention_chunk / _fp8) lets one workgroup per 16-token query tile walk a head's whole
+ * context; the short schedule splits the keys but ends at 32 rows per KV head.  This one runs the tile schedule's
+ * workgroup over one partition of PL slots: the grid is ((query tile, partition), KV head x head group, sequence),
+ * every workgroup leaves an unnormalised fp32 result with its max and sum per (token, query head) row in the partial
+ * scratch, and a second kernel merges the ceil(limit(token) / PL) partitions of a row in ascending order.
+ * Semantics are F5's text above, word for word (visibility rule, plain softmax with fp32 statistics and accumulation,
+ * output rounded once, a row that sees nothing is 0, every output element of every token is written, the metric
+ * rule with its single fixed-order add per slot: the same metric kernel runs behind every schedule).  The schedules
+ * sum in different orders: their outputs agree to rounding, not bit for bit.
+ *   _split_partition  PL: a multiple of 32 and a function of max_context_len and max_query_len alone (1024, doubled
+ *                     until ceil(max_context_len / PL) * ceil(max_query_len / 16) <= 32 or one partition is left) --
+ *                     a sequence's result does not depend on who else is in the batch, given the same two maxima,
+ *                     and the same call gives the same bits.
+ *   _split_workspace_bytes  size of the partial scratch (16-byte aligned):
+ *                     nparts * num_tokens * num_heads * (head_size + 2) * 4 with nparts = ceil(max_context_len / PL);
+ *                     0 when nparts <= 1.
+ * One entry for kv_cache_dtype 0, 1 and 2 (kv_block_stride in elements / in bytes as in the entries above; the fp8
+ * dequantisation rule is kvc_paged_attention_chunk_fp8's).  Any number of rows is accepted, also R <= 32.  When the
+ * rule leaves one partition the entry launches exactly what kvc_paged_attention_chunk / _fp8 launch: bit-identical.
+ * KVC_ERR_INVALID, nothing launched: kv_cache_dtype other than 0 / 1 / 2; with 0 a k_scale or v_scale other than 1,
+ * with 1 / 2 a scale that is not finite and > 0; every refusal of kvc_paged_attention_chunk; with more than one
+ * partition a partial scratch that is too small or not 16-byte aligned.
+ * --------------------------------------------------------------------------------- */
+int32_t kvc_paged_attention_chunk_split_partition(int32_t max_context_len, int32_t max_query_len);
+size_t kvc_paged_attention_chunk_split_workspace_bytes(int32_t num_tokens, int32_t num_heads, int32_t head_size,
+                                                       int32_t max_query_len, int32_t max_context_len);
+int kvc_paged_attention_chunk_split(const kvc_attention_chunk_params* p, float k_scale, float v_scale, void* partial,
+                                    size_t partial_bytes, kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

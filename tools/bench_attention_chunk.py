@@ -16,7 +16,13 @@ in one process, and both against decode x nq; batch 16 at contexts 4k and 32k, o
 at 4k.  The traffic is then counted per CALL (2 * hd * e bytes per visible slot, read once), and the largest
 difference between the two schedules' outputs is recorded next to the times.  With --kv-cache-dtype fp8_*: the two
 schedules and the decode calls read the fp8 cache, and a third alternating leg times the short schedule over the
-2-byte cache of the same geometry (short_auto_ms; fp8_short_over_auto_short is the ratio of the two medians)."""
+2-byte cache of the same geometry (short_auto_ms; fp8_short_over_auto_short is the ratio of the two medians).
+
+--nq 16,32,64,128: query blocks with more than 32 rows per KV head in every configuration.  schedule="split" against
+schedule="tile", batches of 4 launches of one schedule between a pair of events, the two schedules in turn, medians of
+40 batches; the same grid (both layouts, with and without the metric, batch 1 and 64 at 4k / nq 16), over the fp8 cache
+with --kv-cache-dtype fp8_*.  Traffic as in the first leg (per visible slot and query tile), the partition length the
+library chose and the largest difference between the two schedules' outputs are recorded next to the times."""
 import argparse
 import json
 import os
@@ -29,6 +35,7 @@ import torch  # noqa: E402
 
 import vllm_kvcompress_amd as kvc  # noqa: E402
 from vllm_kvcompress_amd import _custom_ops as ops  # noqa: E402
+from vllm_kvcompress_amd import _lib  # noqa: E402
 
 S, HQ, HKV, HD, BS, TILE, PEAK = 16, 32, 8, 128, 16, 16, 8e12
 
@@ -48,8 +55,9 @@ def timed(fn, warmup, reps):
     return statistics.median(ms), min(ms), max(ms)
 
 
-def timed_alternating(*fns, warmup, reps):
-    """the given calls launch by launch in turn (what else runs on the machine hits all alike) -> a (median, min, max) each"""
+def timed_alternating(*fns, warmup, reps, batch=1):
+    """the given calls in turn, `batch` launches of one between a pair of events (what else runs on the machine hits all
+    alike) -> a (median, min, max) of the time per launch each"""
     for _ in range(warmup):
         for fn in fns:
             fn()
@@ -59,10 +67,11 @@ def timed_alternating(*fns, warmup, reps):
         for fn, acc in zip(fns, ms):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             a.record()
-            fn()
+            for _ in range(batch):
+                fn()
             b.record()
             b.synchronize()
-            acc.append(a.elapsed_time(b))
+            acc.append(a.elapsed_time(b) / batch)
     return tuple((statistics.median(m), min(m), max(m)) for m in ms)
 
 
@@ -85,7 +94,7 @@ def make_cache(ctx, dev, gen, kvd="auto"):
     return kc, vc, bt, lens, pos, kc8, vc8
 
 
-def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False):
+def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=False):
     kc, vc, bt, lens, pos, kc8, vc8 = state
     fp8 = kvd != "auto"
     dkc, dvc = (kc8, vc8) if fp8 else (kc, vc)          # what the decode baseline reads
@@ -124,6 +133,24 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False):
                                            step_last[j], buf, BS, ctx, None, kvd, 1.0, 1.0, False)
 
     extra = {}
+    tiles = (nq + TILE - 1) // TILE
+    visible = sum(max(0, ctx - (nq - 1 - min(nq, TILE * (t + 1)) + 1)) for t in range(tiles))    # per head, over the query tiles
+    if split:
+        # the split schedule against the tile one (more than 32 rows per KV head: the short schedule does not apply)
+        sched = chunk_fp8 if fp8 else chunk
+        (s_ms, s_lo, s_hi), (t_ms, t_lo, t_hi) = timed_alternating(lambda: sched("split"), lambda: sched("tile"), warmup=5,
+                                                                   reps=40, batch=4)
+        o_s, o_t = torch.empty_like(q), torch.empty_like(q)
+        sched("split", o_s)
+        sched("tile", o_t)
+        byts = S * HKV * visible * 2 * HD * (1 if fp8 else 2)
+        pl = _lib.load().kvc_paged_attention_chunk_split_partition(ctx, nq)
+        return dict(layout=kvc.block_layout(), kv_cache_dtype=kvd, batch=S, ctx=ctx, nq=nq, metrics=with_metric,
+                    partition_len=pl, partitions=-(-ctx // pl), split_ms=s_ms, split_ms_min=s_lo, split_ms_max=s_hi,
+                    tile_ms=t_ms, tile_ms_min=t_lo, tile_ms_max=t_hi, tile_over_split=t_ms / s_ms,
+                    tile_algorithmic_bytes=byts, split_fraction_of_8TBps=byts / (s_ms * 1e-3) / PEAK,
+                    tile_fraction_of_8TBps=byts / (t_ms * 1e-3) / PEAK,
+                    split_vs_tile_max_abs_diff=float((o_s.float() - o_t.float()).abs().max()), out_tolerance=2e-3)
     if short:
         # fp8: short and tile over the fp8 cache, and the short schedule over the 2-byte cache of the same geometry
         sched = chunk_fp8 if fp8 else chunk
@@ -151,8 +178,6 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False):
     else:
         c_ms, c_lo, c_hi = timed(chunk, 3, 20)
     d_ms, d_lo, d_hi = timed(decode, 1, 5)
-    tiles = (nq + TILE - 1) // TILE
-    visible = sum(max(0, ctx - (nq - 1 - min(nq, TILE * (t + 1)) + 1)) for t in range(tiles))    # per head
     byts = S * HKV * visible * 2 * HD * (1 if fp8 else 2)
     return dict(layout=kvc.block_layout(), batch=S, ctx=ctx, nq=nq, metrics=with_metric, chunk_ms=c_ms, chunk_ms_min=c_lo,
                 chunk_ms_max=c_hi, decode_x_nq_ms=d_ms, decode_x_nq_ms_min=d_lo, decode_x_nq_ms_max=d_hi,
@@ -165,7 +190,8 @@ def main():
     ap.add_argument("--json", default=None)
     ap.add_argument("--only", default=None, help="ctx,nq: a single configuration")
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8_e4m3", "fp8_e5m2"))
-    ap.add_argument("--nq", default=None, help="short query blocks, e.g. 1,2,4,8: the short schedule against the tile one")
+    ap.add_argument("--nq", default=None, help="1,2,4,8: the short schedule against the tile one; 16,32,64,128 (more than 32 rows per "
+                    "KV head throughout): the split schedule against the tile one")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("bench_attention_chunk: needs a GPU (nothing is estimated)")
@@ -173,9 +199,12 @@ def main():
     gen = torch.Generator(device=dev)
     gen.manual_seed(0)
     cfgs = [(c, n) for c in (4096, 32768) for n in (16, 64, 256)]
-    short = args.nq is not None
-    if short:
+    short = split = False
+    if args.nq is not None:
         cfgs = [(c, int(n)) for c in (4096, 32768) for n in args.nq.split(",")]
+        # more than 32 rows per KV head in every configuration: the split schedule's leg, otherwise the short one's
+        split = all(n * (HQ // HKV) > 32 for _, n in cfgs)
+        short = not split
     if args.only:
         cfgs = [tuple(int(v) for v in args.only.split(","))]
     res = []
@@ -185,16 +214,16 @@ def main():
             kvc.set_block_layout(layout)          # (random values: the same buffers serve either layout)
             for nq in [n for c, n in cfgs if c == ctx]:
                 for with_metric in (False, True):
-                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short)
+                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short, split)
                     res.append(r)
                     print(json.dumps(r), flush=True)
         del state
     kvc.set_block_layout("reference")
     global S
-    for batch in (1, 64) if short and not args.only else ():
+    for batch in (1, 64) if (short or split) and not args.only else ():
         S = batch
         state = make_cache(4096, dev, gen, args.kv_cache_dtype)
-        r = run(4096, 4, False, state, dev, gen, args.kv_cache_dtype, short=True)
+        r = run(4096, 16 if split else 4, False, state, dev, gen, args.kv_cache_dtype, short, split)
         res.append(r)
         print(json.dumps(r), flush=True)
         del state

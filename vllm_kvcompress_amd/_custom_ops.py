@@ -678,7 +678,8 @@ def reserve_attention_chunk_scratch(device, num_tokens: int, num_heads: int, *, 
     """Pre-size the row-statistics scratch of ``paged_attention_kvc_chunk`` for the largest token batch the
     engine will run, so the op never allocates while serving or inside a HIP-graph capture.  With ``num_seqs`` /
     ``head_size`` / ``max_query_len`` / ``max_context_len`` also the partial scratch of the short schedule (the
-    per-partition results of calls with at most 32 (token, query head) rows per KV head) for the largest such call."""
+    per-partition results of calls with at most 32 (token, query head) rows per KV head) for the largest such call,
+    and that of the split schedule (``schedule="split"``: per partition, token and query head) for ``num_tokens``."""
     lib = _lib.load()
     reserve_workspace(torch.device(device), lib.kvc_paged_attention_chunk_workspace_bytes(
         int(num_tokens), int(num_heads)) + 256, "attn_chunk")
@@ -686,6 +687,9 @@ def reserve_attention_chunk_scratch(device, num_tokens: int, num_heads: int, *, 
         reserve_workspace(torch.device(device), lib.kvc_paged_attention_chunk_short_workspace_bytes(
             int(num_seqs), int(num_heads), int(head_size), int(max_query_len), int(max_context_len)) + 256,
             "attn_chunk_short")
+        reserve_workspace(torch.device(device), lib.kvc_paged_attention_chunk_split_workspace_bytes(
+            int(num_tokens), int(num_heads), int(head_size), int(max_query_len), int(max_context_len)) + 256,
+            "attn_chunk_split")
 
 
 def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: int, scale: float,
@@ -716,11 +720,16 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     follow-up turn) the keys are split over workgroups and waves and a second kernel merges the partitions
     (``kvc_paged_attention_chunk_short``, over an fp8 cache ``kvc_paged_attention_chunk_short_fp8``,
     include/kvc_mi355x.h; a call that is not eligible raises); ``"auto"`` takes the short schedule exactly when the
-    call is eligible, whatever the cache type.  Same semantics either way; the two sum in different orders, so
-    their outputs agree to rounding."""
+    call is eligible, whatever the cache type, and the tile schedule otherwise; ``"split"`` -- the tile schedule's
+    workgroups over key partitions of ``kvc_paged_attention_chunk_split_partition(max_context_len, max_query_len)``
+    slots, merged by a second kernel (``kvc_paged_attention_chunk_split``; any number of rows, any cache type; with one
+    partition it IS the tile schedule): for more than 32 rows per KV head on a long context, where the tile schedule
+    leaves a head's whole context to one workgroup.  Same semantics every way; the schedules sum in different orders,
+    so their outputs agree to rounding."""
     lib = _lib.load()
-    if schedule not in ("auto", "tile", "short"):
-        raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r}: expected \"auto\", \"tile\" or \"short\"")
+    if schedule not in ("auto", "tile", "short", "split"):
+        raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r}: expected \"auto\", \"tile\", \"short\" "
+                           "or \"split\"")
     kvds = {"auto": 0, "fp8": 1, "fp8_e4m3": 1, "fp8_e5m2": 2}
     if kv_cache_dtype not in kvds:
         raise RuntimeError(f"Unsupported data type of kv cache: {kv_cache_dtype}")
@@ -783,7 +792,13 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     short = schedule == "short" or (schedule == "auto" and bool(eligible(
         p.num_heads, p.num_kv_heads, p.max_query_len, p.kv_cache_dtype)))
     with on_device(query.device):
-        if short:
+        if schedule == "split":
+            pbytes = lib.kvc_paged_attention_chunk_split_workspace_bytes(num_tokens, num_heads, head_size,
+                                                                         p.max_query_len, p.max_context_len)
+            part = workspace(query.device, pbytes + 256, "attn_chunk_split")
+            _lib.check(lib.kvc_paged_attention_chunk_split(p, float(k_scale), float(v_scale), part.data_ptr(), pbytes,
+                                                           _stream(query)))
+        elif short:
             pbytes = lib.kvc_paged_attention_chunk_short_workspace_bytes(num_seqs, num_heads, head_size,
                                                                          p.max_query_len, p.max_context_len)
             part = workspace(query.device, pbytes + 256, "attn_chunk_short")
