@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 13
+#define KVC_ABI_VERSION 14
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -947,6 +947,25 @@ size_t kvc_paged_attention_chunk_split_workspace_bytes(int32_t num_tokens, int32
                                                        int32_t max_query_len, int32_t max_context_len);
 int kvc_paged_attention_chunk_split(const kvc_attention_chunk_params* p, float k_scale, float v_scale, void* partial,
                                     size_t partial_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * The short schedule for three and four row tiles (ABI version 14): the "wide" schedule,
+ *   32 < R = max_query_len * (num_heads / num_kv_heads) <= 64
+ * (5 .. 8 tokens at 8 query heads per KV head, 9 .. 16 at 4: verifying draft tokens at the shapes the short schedule
+ * ends below).  Work split, partition length (_short_partition), partial scratch (_short_workspace_bytes), combine
+ * kernel, metric kernel and semantics are those of kvc_paged_attention_chunk_short: a workgroup owns one partition of
+ * PL slots of one (sequence, KV head) and ALL R rows, every K/V byte is read once per call.  The kernel is its own:
+ * the head's Q rows live in an LDS tile instead of registers.  Caches in the query's dtype only.
+ *   _wide_eligible  1 if the call may take this entry (1 <= R <= 64, kv_cache_dtype 0, num_heads a multiple of
+ *                   num_kv_heads), else 0.
+ * With R <= 32 the entry calls kvc_paged_attention_chunk_short: bit-identical.  KVC_ERR_INVALID, nothing launched:
+ * an fp8 cache (kv_cache_dtype != 0), more than 64 rows, every refusal of kvc_paged_attention_chunk, with more than
+ * one partition a partial scratch that is too small or not 16-byte aligned.
+ * --------------------------------------------------------------------------------- */
+int32_t kvc_paged_attention_chunk_wide_eligible(int32_t num_heads, int32_t num_kv_heads, int32_t max_query_len,
+                                                int32_t kv_cache_dtype);
+int kvc_paged_attention_chunk_wide(const kvc_attention_chunk_params* p, void* partial, size_t partial_bytes,
+                                   kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

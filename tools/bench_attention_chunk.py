@@ -22,7 +22,13 @@ schedules and the decode calls read the fp8 cache, and a third alternating leg t
 schedule="tile", batches of 4 launches of one schedule between a pair of events, the two schedules in turn, medians of
 40 batches; the same grid (both layouts, with and without the metric, batch 1 and 64 at 4k / nq 16), over the fp8 cache
 with --kv-cache-dtype fp8_*.  Traffic as in the first leg (per visible slot and query tile), the partition length the
-library chose and the largest difference between the two schedules' outputs are recorded next to the times."""
+library chose and the largest difference between the two schedules' outputs are recorded next to the times.
+
+--wide --nq 5,6,8 --heads 70b (Llama-3-70B heads, 64 query / 8 KV) or --wide --nq 9,12,16 (8B heads): 33 .. 64 rows per KV
+head.  schedule="wide" against schedule="tile" and schedule="split", launches as in the split leg (batches of 4 between
+a pair of events, the three schedules in turn, medians of 40); both layouts without the metric, one row with the metric
+per context, batch 1 and 64 at 4k for the first nq.  The traffic is counted per CALL as in the short leg, and the
+largest difference between the wide and the tile outputs is recorded next to the times."""
 import argparse
 import json
 import os
@@ -94,7 +100,7 @@ def make_cache(ctx, dev, gen, kvd="auto"):
     return kc, vc, bt, lens, pos, kc8, vc8
 
 
-def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=False):
+def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=False, wide=False):
     kc, vc, bt, lens, pos, kc8, vc8 = state
     fp8 = kvd != "auto"
     dkc, dvc = (kc8, vc8) if fp8 else (kc, vc)          # what the decode baseline reads
@@ -135,6 +141,20 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=Fa
     extra = {}
     tiles = (nq + TILE - 1) // TILE
     visible = sum(max(0, ctx - (nq - 1 - min(nq, TILE * (t + 1)) + 1)) for t in range(tiles))    # per head, over the query tiles
+    if wide:
+        (w_ms, w_lo, w_hi), (t_ms, t_lo, t_hi), (s_ms, s_lo, s_hi) = timed_alternating(
+            lambda: chunk("wide"), lambda: chunk("tile"), lambda: chunk("split"), warmup=5, reps=40, batch=4)
+        o_w, o_t = torch.empty_like(q), torch.empty_like(q)
+        chunk("wide", o_w)
+        chunk("tile", o_t)
+        byts = S * HKV * ctx * 2 * HD * 2
+        return dict(layout=kvc.block_layout(), heads=[HQ, HKV], batch=S, ctx=ctx, nq=nq, metrics=with_metric,
+                    wide_ms=w_ms, wide_ms_min=w_lo, wide_ms_max=w_hi, tile_ms=t_ms, tile_ms_min=t_lo, tile_ms_max=t_hi,
+                    split_ms=s_ms, split_ms_min=s_lo, split_ms_max=s_hi, tile_over_wide=t_ms / w_ms,
+                    split_over_wide=s_ms / w_ms, call_algorithmic_bytes=byts,
+                    wide_fraction_of_8TBps=byts / (w_ms * 1e-3) / PEAK, tile_fraction_of_8TBps=byts / (t_ms * 1e-3) / PEAK,
+                    split_fraction_of_8TBps=byts / (s_ms * 1e-3) / PEAK,
+                    wide_vs_tile_max_abs_diff=float((o_w.float() - o_t.float()).abs().max()), out_tolerance=2e-3)
     if split:
         # the split schedule against the tile one (more than 32 rows per KV head: the short schedule does not apply)
         sched = chunk_fp8 if fp8 else chunk
@@ -192,7 +212,11 @@ def main():
     ap.add_argument("--kv-cache-dtype", default="auto", choices=("auto", "fp8_e4m3", "fp8_e5m2"))
     ap.add_argument("--nq", default=None, help="1,2,4,8: the short schedule against the tile one; 16,32,64,128 (more than 32 rows per "
                     "KV head throughout): the split schedule against the tile one")
+    ap.add_argument("--heads", default="8b", choices=("8b", "70b"), help="Llama-3-8B (32 / 8) or Llama-3-70B (64 / 8) heads")
+    ap.add_argument("--wide", action="store_true", help="with --nq (33 .. 64 rows per KV head): wide against tile and split")
     args = ap.parse_args()
+    global S, HQ
+    HQ = 64 if args.heads == "70b" else 32
     if not torch.cuda.is_available():
         raise SystemExit("bench_attention_chunk: needs a GPU (nothing is estimated)")
     dev = "cuda:0"
@@ -203,8 +227,11 @@ def main():
     if args.nq is not None:
         cfgs = [(c, int(n)) for c in (4096, 32768) for n in args.nq.split(",")]
         # more than 32 rows per KV head in every configuration: the split schedule's leg, otherwise the short one's
-        split = all(n * (HQ // HKV) > 32 for _, n in cfgs)
-        short = not split
+        split = all(n * (HQ // HKV) > 32 for _, n in cfgs) and not args.wide
+        short = not split and not args.wide
+    if args.wide and (args.nq is None or args.kv_cache_dtype != "auto" or
+                      not all(32 < n * (HQ // HKV) <= 64 for _, n in cfgs)):
+        raise SystemExit("bench_attention_chunk: --wide takes --nq with 33 .. 64 rows per KV head over a 2-byte cache")
     if args.only:
         cfgs = [tuple(int(v) for v in args.only.split(","))]
     res = []
@@ -212,18 +239,21 @@ def main():
         state = make_cache(ctx, dev, gen, args.kv_cache_dtype)
         for layout in ("reference", "slot_major"):
             kvc.set_block_layout(layout)          # (random values: the same buffers serve either layout)
-            for nq in [n for c, n in cfgs if c == ctx]:
+            nqs = [n for c, n in cfgs if c == ctx]
+            for nq in nqs:
                 for with_metric in (False, True):
-                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short, split)
+                    if args.wide and with_metric and (layout != "reference" or nq != nqs[0]):
+                        continue                  # one row with the metric per context
+                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short, split, args.wide)
                     res.append(r)
                     print(json.dumps(r), flush=True)
         del state
     kvc.set_block_layout("reference")
-    global S
-    for batch in (1, 64) if (short or split) and not args.only else ():
+    for batch in (1, 64) if (short or split or args.wide) and not args.only else ():
         S = batch
         state = make_cache(4096, dev, gen, args.kv_cache_dtype)
-        r = run(4096, 16 if split else 4, False, state, dev, gen, args.kv_cache_dtype, short, split)
+        r = run(4096, cfgs[0][1] if args.wide else 16 if split else 4, False, state, dev, gen, args.kv_cache_dtype, short,
+                split, args.wide)
         res.append(r)
         print(json.dumps(r), flush=True)
         del state
