@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 14
+#define KVC_ABI_VERSION 15
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -966,6 +966,26 @@ int32_t kvc_paged_attention_chunk_wide_eligible(int32_t num_heads, int32_t num_k
                                                 int32_t kv_cache_dtype);
 int kvc_paged_attention_chunk_wide(const kvc_attention_chunk_params* p, void* partial, size_t partial_bytes,
                                    kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * The wide schedule over an fp8 cache (ABI version 15): kvc_paged_attention_chunk_wide for kv_cache_dtype 1 (OCP
+ * e4m3fn bytes) or 2 (e5m2 bytes), in both block layouts, 32 < R <= 64.  Blocks, kv_block_stride in BYTES and the
+ * dequantisation rule are those of kvc_paged_attention_chunk_fp8 -- bytes convert exactly to the query's dtype, logits
+ * = scale * k_scale * (query . k8), out = v_scale * (sum p . v8) / sum p, the row statistics and the partial scratch
+ * without v_scale --; work split, partition length (_short_partition), partial scratch (_short_workspace_bytes),
+ * combine kernel, metric kernel and semantics are those of the wide entry above.  The kernel is its own (DESIGN.md
+ * 3.8): the wide kernel's Q tile in the LDS, the fp8 short kernel's byte geometry of a step.
+ *   _wide_fp8_eligible  1 if the call may take this entry (1 <= R <= 64, kv_cache_dtype 1 or 2, num_heads a multiple
+ *                       of num_kv_heads), else 0.
+ * With R <= 32 the entry calls kvc_paged_attention_chunk_short_fp8: bit-identical.  KVC_ERR_INVALID, nothing launched:
+ * kv_cache_dtype 0 (that cache goes to kvc_paged_attention_chunk_wide) or anything but 1 / 2, a scale that is not
+ * finite and > 0, more than 64 rows, every refusal of kvc_paged_attention_chunk_fp8, with more than one partition a
+ * partial scratch that is missing, too small or not 16-byte aligned.
+ * --------------------------------------------------------------------------------- */
+int32_t kvc_paged_attention_chunk_wide_fp8_eligible(int32_t num_heads, int32_t num_kv_heads, int32_t max_query_len,
+                                                    int32_t kv_cache_dtype);
+int kvc_paged_attention_chunk_wide_fp8(const kvc_attention_chunk_params* p, float k_scale, float v_scale, void* partial,
+                                       size_t partial_bytes, kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -28,7 +28,9 @@ library chose and the largest difference between the two schedules' outputs are 
 head.  schedule="wide" against schedule="tile" and schedule="split", launches as in the split leg (batches of 4 between
 a pair of events, the three schedules in turn, medians of 40); both layouts without the metric, one row with the metric
 per context, batch 1 and 64 at 4k for the first nq.  The traffic is counted per CALL as in the short leg, and the
-largest difference between the wide and the tile outputs is recorded next to the times."""
+largest difference between the wide and the tile outputs is recorded next to the times.  With --kv-cache-dtype fp8_* the
+three schedules read the fp8 cache, and a fourth alternating leg times the wide schedule over the 2-byte cache of the
+same geometry (wide_auto_ms; fp8_wide_over_auto_wide is the ratio of the two medians)."""
 import argparse
 import json
 import os
@@ -142,13 +144,19 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=Fa
     tiles = (nq + TILE - 1) // TILE
     visible = sum(max(0, ctx - (nq - 1 - min(nq, TILE * (t + 1)) + 1)) for t in range(tiles))    # per head, over the query tiles
     if wide:
-        (w_ms, w_lo, w_hi), (t_ms, t_lo, t_hi), (s_ms, s_lo, s_hi) = timed_alternating(
-            lambda: chunk("wide"), lambda: chunk("tile"), lambda: chunk("split"), warmup=5, reps=40, batch=4)
+        # fp8: wide, tile and split over the fp8 cache, and the wide schedule over the 2-byte cache of the same geometry
+        sched = chunk_fp8 if fp8 else chunk
+        fns = [lambda: sched("wide"), lambda: sched("tile"), lambda: sched("split")] + ([lambda: chunk("wide")] if fp8 else [])
+        (w_ms, w_lo, w_hi), (t_ms, t_lo, t_hi), (s_ms, s_lo, s_hi), *rest = timed_alternating(*fns, warmup=5, reps=40, batch=4)
         o_w, o_t = torch.empty_like(q), torch.empty_like(q)
-        chunk("wide", o_w)
-        chunk("tile", o_t)
-        byts = S * HKV * ctx * 2 * HD * 2
-        return dict(layout=kvc.block_layout(), heads=[HQ, HKV], batch=S, ctx=ctx, nq=nq, metrics=with_metric,
+        sched("wide", o_w)
+        sched("tile", o_t)
+        byts = S * HKV * ctx * 2 * HD * (1 if fp8 else 2)
+        if fp8:
+            (a_ms, a_lo, a_hi), = rest
+            extra = dict(kv_cache_dtype=kvd, wide_auto_ms=a_ms, wide_auto_ms_min=a_lo, wide_auto_ms_max=a_hi,
+                         fp8_wide_over_auto_wide=w_ms / a_ms)
+        return dict(layout=kvc.block_layout(), heads=[HQ, HKV], batch=S, ctx=ctx, nq=nq, metrics=with_metric, **extra,
                     wide_ms=w_ms, wide_ms_min=w_lo, wide_ms_max=w_hi, tile_ms=t_ms, tile_ms_min=t_lo, tile_ms_max=t_hi,
                     split_ms=s_ms, split_ms_min=s_lo, split_ms_max=s_hi, tile_over_wide=t_ms / w_ms,
                     split_over_wide=s_ms / w_ms, call_algorithmic_bytes=byts,
@@ -229,9 +237,8 @@ def main():
         # more than 32 rows per KV head in every configuration: the split schedule's leg, otherwise the short one's
         split = all(n * (HQ // HKV) > 32 for _, n in cfgs) and not args.wide
         short = not split and not args.wide
-    if args.wide and (args.nq is None or args.kv_cache_dtype != "auto" or
-                      not all(32 < n * (HQ // HKV) <= 64 for _, n in cfgs)):
-        raise SystemExit("bench_attention_chunk: --wide takes --nq with 33 .. 64 rows per KV head over a 2-byte cache")
+    if args.wide and (args.nq is None or not all(32 < n * (HQ // HKV) <= 64 for _, n in cfgs)):
+        raise SystemExit("bench_attention_chunk: --wide takes --nq with 33 .. 64 rows per KV head")
     if args.only:
         cfgs = [tuple(int(v) for v in args.only.split(","))]
     res = []

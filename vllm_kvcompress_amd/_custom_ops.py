@@ -726,8 +726,8 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     partition it IS the tile schedule): for more than 32 rows per KV head on a long context, where the tile schedule
     leaves a head's whole context to one workgroup; ``"wide"`` -- the short schedule's work split for up to 64 rows per
     KV head (5 .. 8 tokens at 8 query heads per KV head, 9 .. 16 at 4), by a kernel that keeps the head's Q rows in the
-    LDS (``kvc_paged_attention_chunk_wide``; caches in the query's dtype only; with at most 32 rows it IS the short
-    schedule; more than 64 rows or an fp8 cache raise; ``"auto"`` never takes it).  Same semantics every way; the
+    LDS (``kvc_paged_attention_chunk_wide``, over an fp8 cache ``kvc_paged_attention_chunk_wide_fp8``; with at most 32
+    rows it IS the short schedule; more than 64 rows raise; ``"auto"`` never takes it).  Same semantics every way; the
     schedules sum in different orders, so their outputs agree to rounding."""
     lib = _lib.load()
     if schedule not in ("auto", "tile", "short", "split", "wide"):
@@ -805,7 +805,11 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
             pbytes = lib.kvc_paged_attention_chunk_short_workspace_bytes(num_seqs, num_heads, head_size,
                                                                          p.max_query_len, p.max_context_len)
             part = workspace(query.device, pbytes + 256, "attn_chunk_short")
-            _lib.check(lib.kvc_paged_attention_chunk_wide(p, part.data_ptr(), pbytes, _stream(query)))
+            if p.kv_cache_dtype == 0:
+                _lib.check(lib.kvc_paged_attention_chunk_wide(p, part.data_ptr(), pbytes, _stream(query)))
+            else:
+                _lib.check(lib.kvc_paged_attention_chunk_wide_fp8(p, float(k_scale), float(v_scale), part.data_ptr(),
+                                                                  pbytes, _stream(query)))
         elif short:
             pbytes = lib.kvc_paged_attention_chunk_short_workspace_bytes(num_seqs, num_heads, head_size,
                                                                          p.max_query_len, p.max_context_len)
