@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 15
+#define KVC_ABI_VERSION 16
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -986,6 +986,26 @@ int32_t kvc_paged_attention_chunk_wide_fp8_eligible(int32_t num_heads, int32_t n
                                                     int32_t kv_cache_dtype);
 int kvc_paged_attention_chunk_wide_fp8(const kvc_attention_chunk_params* p, float k_scale, float v_scale, void* partial,
                                        size_t partial_bytes, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * The metric pass alone, in "row form" (ABI version 16), for calls with
+ *   R = max_query_len * (num_heads / num_kv_heads) <= 64
+ * over caches of every kv_cache_dtype (0: the query's dtype; 1 / 2: e4m3fn / e5m2 bytes) in both block layouts.  It
+ * adds to p->metrics what the metric kernel behind the entries above adds -- the same rule: per slot, sum p^2 (use_l2)
+ * or sum p over the rows (token, query head) of the slot's KV head that see the slot and whose metric window holds
+ * kv_position[slot]; one fp32 add per reached slot in an order that depends on the rows alone, no atomics, slots no
+ * row reaches are not written -- by a kernel whose MFMA tiles hold 16 ROWS r = token * qpk + query head where that one
+ * holds 16 tokens of one query head.  The two kernels sum in different orders: they agree to rounding.
+ * p->workspace is READ: it must hold the row statistics an output pass with the same params left there -- any of the
+ * entries above, which write them whether or not their own p->metrics is NULL.  The intended pairing is that entry
+ * with metrics = NULL, then this one with metrics set, on the same stream.  k_scale is the output pass's (kv_cache_dtype
+ * 0: 1); out, value_cache and use of v_scale: none (out and value_cache are only checked like the output entries do).
+ * KVC_ERR_INVALID, nothing launched: metrics == NULL; more than 64 rows; kv_cache_dtype other than 0 / 1 / 2;
+ * kv_cache_dtype 0 with k_scale != 1; a k_scale that is not finite and > 0; every refusal of
+ * kvc_paged_attention_chunk / _fp8 (ALiBi slopes, head sizes other than 64 / 128, block sizes other than 16 / 32,
+ * alignment, a workspace smaller than _workspace_bytes).  num_seqs = 0, no tokens or max_context_len <= 0: no-op.
+ * --------------------------------------------------------------------------------- */
+int kvc_paged_attention_chunk_metric_rows(const kvc_attention_chunk_params* p, float k_scale, kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

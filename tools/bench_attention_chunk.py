@@ -30,7 +30,14 @@ a pair of events, the three schedules in turn, medians of 40); both layouts with
 per context, batch 1 and 64 at 4k for the first nq.  The traffic is counted per CALL as in the short leg, and the
 largest difference between the wide and the tile outputs is recorded next to the times.  With --kv-cache-dtype fp8_* the
 three schedules read the fp8 cache, and a fourth alternating leg times the wide schedule over the 2-byte cache of the
-same geometry (wide_auto_ms; fp8_wide_over_auto_wide is the ratio of the two medians)."""
+same geometry (wide_auto_ms; fp8_wide_over_auto_wide is the ratio of the two medians).
+
+--metric-schedule tile|rows|both with --nq (at most 64 rows per KV head; --wide for 33 .. 64): the metric passes behind
+ONE output schedule ("short" up to 32 rows, "wide" beyond).  The call without the metric, with metric_schedule="tile"
+and with metric_schedule="rows" in turn (batches of 4 launches between a pair of events, medians of 40); a metric pass
+is its call minus the call without the metric, its traffic the K bytes of the call (hd * e per slot).  Both layouts,
+batch 16 at both contexts, batch 1 and 64 at 4k for the first nq; the largest relative difference between the two
+metrics (from zeros) is recorded next to the times."""
 import argparse
 import json
 import os
@@ -102,7 +109,7 @@ def make_cache(ctx, dev, gen, kvd="auto"):
     return kc, vc, bt, lens, pos, kc8, vc8
 
 
-def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=False, wide=False):
+def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=False, wide=False, metric_leg=None):
     kc, vc, bt, lens, pos, kc8, vc8 = state
     fp8 = kvd != "auto"
     dkc, dvc = (kc8, vc8) if fp8 else (kc, vc)          # what the decode baseline reads
@@ -115,14 +122,37 @@ def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=Fa
     metrics = torch.zeros(pos.shape, dtype=torch.float32, device=dev) if with_metric else None
     scale = HD ** -0.5
 
-    def chunk(schedule="tile", out=out):
+    def chunk(schedule="tile", out=out, metrics=metrics, metric_schedule="tile"):
         ops.paged_attention_kvc_chunk(out, q, kc, vc, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
-                                      metrics=metrics, use_l2=True, schedule=schedule)
+                                      metrics=metrics, use_l2=True, schedule=schedule, metric_schedule=metric_schedule)
 
-    def chunk_fp8(schedule="tile", out=out):
+    def chunk_fp8(schedule="tile", out=out, metrics=metrics, metric_schedule="tile"):
         ops.paged_attention_kvc_chunk(out, q, kc8, vc8, HKV, scale, bt, lens, pos, qsl, qpos, buf, BS, ctx, nq,
                                       metrics=metrics, use_l2=True, kv_cache_dtype=kvd, k_scale=1.0, v_scale=1.0,
-                                      schedule=schedule)
+                                      schedule=schedule, metric_schedule=metric_schedule)
+
+    if metric_leg:
+        # the two metric passes behind the same output pass, and that pass alone
+        sched = chunk_fp8 if fp8 else chunk
+        rows = nq * (HQ // HKV)
+        name = "wide" if rows > 32 else "short"
+        legs = [m for m in ("tile", "rows") if metric_leg in (m, "both")]
+        fns = [lambda: sched(name, metrics=None)] + [lambda m=m: sched(name, metric_schedule=m) for m in legs]
+        (n_ms, n_lo, n_hi), *rest = timed_alternating(*fns, warmup=5, reps=40, batch=4)
+        kbytes = S * HKV * ctx * HD * (1 if fp8 else 2)
+        r = dict(layout=kvc.block_layout(), heads=[HQ, HKV], kv_cache_dtype=kvd, batch=S, ctx=ctx, nq=nq, rows=rows,
+                 schedule=name, no_metric_ms=n_ms, no_metric_ms_min=n_lo, no_metric_ms_max=n_hi, k_bytes=kbytes)
+        added = {}
+        for m, (c_ms, c_lo, c_hi) in zip(legs, rest):
+            r.update({f"{m}_call_ms": c_ms, f"{m}_call_ms_min": c_lo, f"{m}_call_ms_max": c_hi, f"{m}_metric_ms": c_ms - n_ms,
+                      f"{m}_metric_fraction_of_8TBps_on_K": kbytes / max((c_ms - n_ms) * 1e-3, 1e-12) / PEAK})
+            added[m] = torch.zeros_like(metrics)
+            sched(name, metrics=added[m], metric_schedule=m)
+        if len(legs) == 2:
+            r["tile_over_rows_metric"] = r["tile_metric_ms"] / max(r["rows_metric_ms"], 1e-9)
+            r["rows_vs_tile_max_rel_diff"] = float(((added["rows"] - added["tile"]).abs() /
+                                                    added["tile"].abs().clamp_min(1e-30)).max())
+        return r
 
     # the decode baseline: step j sees context_lens - (nq - 1 - j) slots and has one query per sequence
     q4, out_d = q.view(S, nq, HQ, HD), torch.empty((S, HQ, HD), dtype=q.dtype, device=dev)
@@ -222,6 +252,8 @@ def main():
                     "KV head throughout): the split schedule against the tile one")
     ap.add_argument("--heads", default="8b", choices=("8b", "70b"), help="Llama-3-8B (32 / 8) or Llama-3-70B (64 / 8) heads")
     ap.add_argument("--wide", action="store_true", help="with --nq (33 .. 64 rows per KV head): wide against tile and split")
+    ap.add_argument("--metric-schedule", default=None, choices=("tile", "rows", "both"),
+                    help="with --nq (at most 64 rows per KV head): the metric passes behind one output schedule")
     args = ap.parse_args()
     global S, HQ
     HQ = 64 if args.heads == "70b" else 32
@@ -239,6 +271,8 @@ def main():
         short = not split and not args.wide
     if args.wide and (args.nq is None or not all(32 < n * (HQ // HKV) <= 64 for _, n in cfgs)):
         raise SystemExit("bench_attention_chunk: --wide takes --nq with 33 .. 64 rows per KV head")
+    if args.metric_schedule and (args.nq is None or not all(n * (HQ // HKV) <= 64 for _, n in cfgs)):
+        raise SystemExit("bench_attention_chunk: --metric-schedule takes --nq with at most 64 rows per KV head")
     if args.only:
         cfgs = [tuple(int(v) for v in args.only.split(","))]
     res = []
@@ -248,10 +282,11 @@ def main():
             kvc.set_block_layout(layout)          # (random values: the same buffers serve either layout)
             nqs = [n for c, n in cfgs if c == ctx]
             for nq in nqs:
-                for with_metric in (False, True):
-                    if args.wide and with_metric and (layout != "reference" or nq != nqs[0]):
+                for with_metric in (True,) if args.metric_schedule else (False, True):
+                    if args.wide and with_metric and not args.metric_schedule and (layout != "reference" or nq != nqs[0]):
                         continue                  # one row with the metric per context
-                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short, split, args.wide)
+                    r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short, split, args.wide,
+                            args.metric_schedule)
                     res.append(r)
                     print(json.dumps(r), flush=True)
         del state
@@ -259,8 +294,8 @@ def main():
     for batch in (1, 64) if (short or split or args.wide) and not args.only else ():
         S = batch
         state = make_cache(4096, dev, gen, args.kv_cache_dtype)
-        r = run(4096, cfgs[0][1] if args.wide else 16 if split else 4, False, state, dev, gen, args.kv_cache_dtype, short,
-                split, args.wide)
+        r = run(4096, cfgs[0][1] if args.wide else 16 if split else 4, bool(args.metric_schedule), state, dev, gen,
+                args.kv_cache_dtype, short, split, args.wide, args.metric_schedule)
         res.append(r)
         print(json.dumps(r), flush=True)
         del state

@@ -697,7 +697,8 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
                               kv_metric_buffer_len, block_size: int, max_context_len: int,
                               max_query_len: int, metrics: Optional[torch.Tensor] = None,
                               use_l2: bool = True, alibi_slopes=None, kv_cache_dtype: str = "auto",
-                              k_scale: float = 1.0, v_scale: float = 1.0, schedule: str = "auto") -> None:
+                              k_scale: float = 1.0, v_scale: float = 1.0, schedule: str = "auto",
+                              metric_schedule: str = "tile") -> None:
     """Attention of ``nq_s >= 0`` new tokens per sequence over the per-head paged cache (chunked prefill, a
     follow-up turn on a kept cache, prefix reuse, verifying draft tokens): ``query`` / ``out``
     ``[num_tokens, num_heads, head_size]`` packed over the sequences, sequence ``s`` owning tokens
@@ -728,7 +729,17 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     KV head (5 .. 8 tokens at 8 query heads per KV head, 9 .. 16 at 4), by a kernel that keeps the head's Q rows in the
     LDS (``kvc_paged_attention_chunk_wide``, over an fp8 cache ``kvc_paged_attention_chunk_wide_fp8``; with at most 32
     rows it IS the short schedule; more than 64 rows raise; ``"auto"`` never takes it).  Same semantics every way; the
-    schedules sum in different orders, so their outputs agree to rounding."""
+    schedules sum in different orders, so their outputs agree to rounding.
+
+    ``metric_schedule`` (with ``metrics``): ``"tile"`` -- the metric kernel behind every ``schedule``, whose MFMA tile
+    is 16 tokens of one query head; ``"rows"`` -- for ``max_query_len * (num_heads / num_kv_heads) <= 64``, whatever
+    ``schedule`` resolved to: the chosen entry runs without metrics and ``kvc_paged_attention_chunk_metric_rows`` adds
+    them behind it on the same stream, from the row statistics that entry left, by a kernel whose tile is 16 (token,
+    query head) rows and that reads every K byte once for all rows (more than 64 rows raise; without ``metrics`` it
+    changes nothing).  ``out`` has the same bits either way; the metric is the same rule summed in another order, fixed
+    and identical from run to run.  There is no ``"auto"``: ``"tile"`` is the default."""
+    if metric_schedule not in ("tile", "rows"):
+        raise RuntimeError(f"paged_attention_kvc_chunk: metric_schedule {metric_schedule!r}: expected \"tile\" or \"rows\"")
     lib = _lib.load()
     if schedule not in ("auto", "tile", "short", "split", "wide"):
         raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r}: expected \"auto\", \"tile\", \"short\", "
@@ -794,6 +805,12 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
                 else lib.kvc_paged_attention_chunk_short_fp8_eligible)
     short = schedule == "short" or (schedule == "auto" and bool(eligible(
         p.num_heads, p.num_kv_heads, p.max_query_len, p.kv_cache_dtype)))
+    rows_pass = metric_schedule == "rows" and metrics is not None
+    if rows_pass:
+        if num_heads % p.num_kv_heads == 0 and p.max_query_len * (num_heads // p.num_kv_heads) > 64:
+            raise RuntimeError("paged_attention_kvc_chunk: metric_schedule \"rows\" takes at most 64 (token, query head) "
+                               f"rows per KV head, this call has {p.max_query_len * (num_heads // p.num_kv_heads)}")
+        p.metrics = None                       # the output entry leaves the row statistics; the rows pass adds behind it
     with on_device(query.device):
         if schedule == "split":
             pbytes = lib.kvc_paged_attention_chunk_split_workspace_bytes(num_tokens, num_heads, head_size,
@@ -823,4 +840,7 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
             _lib.check(lib.kvc_paged_attention_chunk(p, _stream(query)))
         else:
             _lib.check(lib.kvc_paged_attention_chunk_fp8(p, float(k_scale), float(v_scale), _stream(query)))
+        if rows_pass:
+            p.metrics = metrics.data_ptr()
+            _lib.check(lib.kvc_paged_attention_chunk_metric_rows(p, float(k_scale), _stream(query)))
     _written(out, metrics)
