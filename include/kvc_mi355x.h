@@ -36,7 +36,7 @@ typedef void* kvc_stream_t; /* hipStream_t */
 /* The ABI this header describes; kvc_abi_version() of the library loaded at run time must return it
  * (kvc_schedule_params grew fields in the middle between versions: a host built against another
  * version must not call in).  The Python binding and tests/cabi/cabi_host.cpp check it at start-up. */
-#define KVC_ABI_VERSION 16
+#define KVC_ABI_VERSION 17
 
 int kvc_abi_version(void);
 const char* kvc_last_error(void);
@@ -1006,6 +1006,39 @@ int kvc_paged_attention_chunk_wide_fp8(const kvc_attention_chunk_params* p, floa
  * alignment, a workspace smaller than _workspace_bytes).  num_seqs = 0, no tokens or max_context_len <= 0: no-op.
  * --------------------------------------------------------------------------------- */
 int kvc_paged_attention_chunk_metric_rows(const kvc_attention_chunk_params* p, float k_scale, kvc_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * F5 for a draft TREE (ABI version 17): the key-split schedules with a caller-given visibility among the new tokens,
+ * for calls with
+ *   R = max_query_len * (num_heads / num_kv_heads) <= 64   and   max_query_len <= 64.
+ * The entries above hard-wire the chain: token j sees slots i < context_lens[s, h] - (nq_s - 1 - j).  Here the call
+ * carries tree_mask, one 64-bit word per query token ([num_tokens]).  For sequence s and KV head h let
+ * base = context_lens[s, h] - nq_s (signed: it is negative for a head with fewer slots than new tokens).  Slot i has
+ * e = i - base, and token t of the sequence sees slot i < context_lens[s, h] iff
+ *   e < 0   (the cached prefix: every token sees all of it),   or   e < nq_s and bit e of tree_mask[t] is set.
+ * No bit is implied: a token that sees itself has its own bit set.  Bits from nq_s up are ignored.  The chain is the
+ * mask (1 << (j + 1)) - 1 for token j, and with it out has the bits of the short / wide entries above and the metric
+ * those of kvc_paged_attention_chunk_metric_rows behind them.
+ * Everything not named here stays F5's, word for word: plain softmax with fp32 statistics and accumulation, output
+ * rounded once, a row that sees nothing is 0, every output element of every token is written.  The metric rule is
+ * unchanged except that "sees" is the rule above: one fixed-order fp32 add per reached slot, no atomics, slots no row
+ * reaches -- a draft slot no token sees among them -- are not written, and the window test kv_position[slot] <=
+ * query_positions[t] - kv_metric_buffer_len[s] uses the positions the caller passes (for a tree: depths).
+ * One entry for kv_cache_dtype 0, 1 and 2 with the scale rules of kvc_paged_attention_chunk_split (kv_block_stride in
+ * elements / in bytes; the fp8 dequantisation rule is kvc_paged_attention_chunk_fp8's).  R <= 32 runs the TREE variant
+ * of the short kernel, 32 < R <= 64 that of the wide kernel; partition length and partial scratch are the short
+ * schedule's (_short_partition, _short_workspace_bytes).  With p->metrics set the entry runs the output pass without
+ * metrics and then the TREE variant of the row-form metric kernel on the same stream.
+ *   _tree_eligible  1 if the call may take this entry (1 <= max_query_len <= 64, R <= 64, num_heads a multiple of
+ *                   num_kv_heads), else 0.
+ * KVC_ERR_INVALID, nothing launched: tree_mask NULL or not 8-byte aligned; more than 64 rows or max_query_len > 64;
+ * kv_cache_dtype other than 0 / 1 / 2; with 0 a k_scale or v_scale other than 1, with 1 / 2 a scale that is not
+ * finite and > 0; every refusal of kvc_paged_attention_chunk / _fp8; with more than one partition a partial scratch
+ * that is too small or not 16-byte aligned.
+ * --------------------------------------------------------------------------------- */
+int32_t kvc_paged_attention_chunk_tree_eligible(int32_t num_heads, int32_t num_kv_heads, int32_t max_query_len);
+int kvc_paged_attention_chunk_tree(const kvc_attention_chunk_params* p, const uint64_t* tree_mask, float k_scale,
+                                   float v_scale, void* partial, size_t partial_bytes, kvc_stream_t stream);
 
 #ifdef __cplusplus
 }

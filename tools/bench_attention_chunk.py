@@ -37,7 +37,16 @@ ONE output schedule ("short" up to 32 rows, "wide" beyond).  The call without th
 and with metric_schedule="rows" in turn (batches of 4 launches between a pair of events, medians of 40); a metric pass
 is its call minus the call without the metric, its traffic the K bytes of the call (hd * e per slot).  Both layouts,
 batch 16 at both contexts, batch 1 and 64 at 4k for the first nq; the largest relative difference between the two
-metrics (from zeros) is recorded next to the times."""
+metrics (from zeros) is recorded next to the times.
+
+--tree --nq 7,15 (8B heads) or --tree --nq 7 --heads 70b (at most 64 rows per KV head): draft-TREE verification.  The
+tree is fixed: nq nodes in heap order, node j's parent is (j - 1) // 2 -- complete binary trees at nq 7 (4 leaves, paths
+of 3) and nq 15 (8 leaves, paths of 4).  One call with tree_mask (the nodes' ancestor words) against the chain call of
+the same shape and nq, and against what a caller without tree_mask has to run: one chain call per root-to-leaf path, each
+over the prefix plus the path's nodes.  The four legs -- tree, chain, the chain call a second time, the per-path calls --
+in turn, batches of 4 launches between a pair of events, medians of 40; chain_again_over_chain is the spread a ratio of
+two legs has by itself.  Both layouts without the metric, one row with the metric (row form on every side) per
+context; over the fp8 cache with --kv-cache-dtype fp8_*."""
 import argparse
 import json
 import os
@@ -107,6 +116,59 @@ def make_cache(ctx, dev, gen, kvd="auto"):
     pos[bt.long().view(-1)] = torch.arange(nblk * BS, dtype=torch.int32, device=dev).view(1, nblk, BS).expand(
         S * HKV, nblk, BS).reshape(-1, BS)
     return kc, vc, bt, lens, pos, kc8, vc8
+
+
+def run_tree(ctx, nq, with_metric, state, dev, gen, kvd):
+    """one tree call of nq nodes against the chain call of the same shape, and against the per-path chain calls"""
+    kc, vc, bt, lens, pos, kc8, vc8 = state
+    fp8 = kvd != "auto"
+    cache = (kc8, vc8) if fp8 else (kc, vc)
+    kw = dict(kv_cache_dtype=kvd, k_scale=1.0, v_scale=1.0) if fp8 else {}
+    rows = nq * (HQ // HKV)
+    name = "wide" if rows > 32 else "short"
+    scale = HD ** -0.5
+    buf = torch.zeros(S, dtype=torch.int32, device=dev)
+    metrics = torch.zeros(pos.shape, dtype=torch.float32, device=dev) if with_metric else None
+    # the tree: nodes in heap order, node j's parent is (j - 1) // 2 -- complete binary trees at nq 7 (4 leaves, 3 levels)
+    # and 15 (8 leaves, 4 levels); a node's word is its parent's plus its own bit, its position the prefix plus its depth
+    words, depth = [], []
+    for j in range(nq):
+        words.append((words[(j - 1) // 2] if j else 0) | (1 << j))
+        depth.append(depth[(j - 1) // 2] + 1 if j else 0)
+    paths = [[i for i in range(nq) if (words[j] >> i) & 1] for j in range(nq) if 2 * j + 1 >= nq]
+    q = torch.randn((S, nq, HQ, HD), device=dev, generator=gen, dtype=torch.float16)
+
+    def call(nodes, tree):
+        """the call that verifies these nodes of every sequence: as a tree (their words), or as a chain (a path)"""
+        d = len(nodes)
+        qn = q[:, nodes].reshape(S * d, HQ, HD).contiguous()
+        out = torch.empty_like(qn)
+        qsl = torch.arange(0, S * d + 1, d, dtype=torch.int32, device=dev)
+        steps = [depth[j] for j in nodes] if tree else list(range(d))
+        qpos = (torch.tensor(steps, dtype=torch.int32, device=dev) + (ctx - nq)).repeat(S)
+        clens = (lens - (nq - d)).contiguous()
+        mask = torch.tensor([words[j] for j in nodes], dtype=torch.int64, device=dev).repeat(S) if tree else None
+        sched = "wide" if d * (HQ // HKV) > 32 else "short"
+        return lambda: ops.paged_attention_kvc_chunk(
+            out, qn, *cache, HKV, scale, bt, clens, pos, qsl, qpos, buf, BS, ctx - (nq - d), d, metrics=metrics, use_l2=True,
+            schedule=sched, metric_schedule="rows", tree_mask=mask, **kw)
+
+    tree_fn, chain_fn = call(list(range(nq)), True), call(list(range(nq)), False)
+    path_fns = [call(p, False) for p in paths]
+
+    def all_paths():
+        for fn in path_fns:
+            fn()
+
+    # the chain call twice: the ratio of its two legs is the spread a ratio of this table has by itself
+    (t_ms, t_lo, t_hi), (c_ms, c_lo, c_hi), (c2_ms, c2_lo, c2_hi), (p_ms, p_lo, p_hi) = timed_alternating(
+        tree_fn, chain_fn, chain_fn, all_paths, warmup=5, reps=40, batch=4)
+    return dict(layout=kvc.block_layout(), heads=[HQ, HKV], kv_cache_dtype=kvd, batch=S, ctx=ctx, nq=nq, rows=rows,
+                schedule=name, metrics=with_metric, tree="binary, heap order", paths=len(paths), path_len=len(paths[0]),
+                tree_ms=t_ms, tree_ms_min=t_lo, tree_ms_max=t_hi, chain_ms=c_ms, chain_ms_min=c_lo, chain_ms_max=c_hi,
+                chain_again_ms=c2_ms, chain_again_ms_min=c2_lo, chain_again_ms_max=c2_hi,
+                per_path_chain_calls_ms=p_ms, per_path_chain_calls_ms_min=p_lo, per_path_chain_calls_ms_max=p_hi,
+                tree_over_chain=t_ms / c_ms, chain_again_over_chain=c2_ms / c_ms, paths_over_tree=p_ms / t_ms)
 
 
 def run(ctx, nq, with_metric, state, dev, gen, kvd="auto", short=False, split=False, wide=False, metric_leg=None):
@@ -254,6 +316,8 @@ def main():
     ap.add_argument("--wide", action="store_true", help="with --nq (33 .. 64 rows per KV head): wide against tile and split")
     ap.add_argument("--metric-schedule", default=None, choices=("tile", "rows", "both"),
                     help="with --nq (at most 64 rows per KV head): the metric passes behind one output schedule")
+    ap.add_argument("--tree", action="store_true", help="with --nq (at most 64 rows per KV head, e.g. 7,15): one tree call "
+                    "against the chain call of the same shape and against one chain call per root-to-leaf path")
     args = ap.parse_args()
     global S, HQ
     HQ = 64 if args.heads == "70b" else 32
@@ -267,8 +331,10 @@ def main():
     if args.nq is not None:
         cfgs = [(c, int(n)) for c in (4096, 32768) for n in args.nq.split(",")]
         # more than 32 rows per KV head in every configuration: the split schedule's leg, otherwise the short one's
-        split = all(n * (HQ // HKV) > 32 for _, n in cfgs) and not args.wide
-        short = not split and not args.wide
+        split = all(n * (HQ // HKV) > 32 for _, n in cfgs) and not args.wide and not args.tree
+        short = not split and not args.wide and not args.tree
+    if args.tree and (args.nq is None or not all(n * (HQ // HKV) <= 64 for _, n in cfgs)):
+        raise SystemExit("bench_attention_chunk: --tree takes --nq with at most 64 rows per KV head")
     if args.wide and (args.nq is None or not all(32 < n * (HQ // HKV) <= 64 for _, n in cfgs)):
         raise SystemExit("bench_attention_chunk: --wide takes --nq with 33 .. 64 rows per KV head")
     if args.metric_schedule and (args.nq is None or not all(n * (HQ // HKV) <= 64 for _, n in cfgs)):
@@ -283,8 +349,14 @@ def main():
             nqs = [n for c, n in cfgs if c == ctx]
             for nq in nqs:
                 for with_metric in (True,) if args.metric_schedule else (False, True):
-                    if args.wide and with_metric and not args.metric_schedule and (layout != "reference" or nq != nqs[0]):
+                    if (args.wide or args.tree) and with_metric and not args.metric_schedule and (
+                            layout != "reference" or nq != nqs[0]):
                         continue                  # one row with the metric per context
+                    if args.tree:
+                        r = run_tree(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype)
+                        res.append(r)
+                        print(json.dumps(r), flush=True)
+                        continue
                     r = run(ctx, nq, with_metric, state, dev, gen, args.kv_cache_dtype, short, split, args.wide,
                             args.metric_schedule)
                     res.append(r)

@@ -698,7 +698,7 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
                               max_query_len: int, metrics: Optional[torch.Tensor] = None,
                               use_l2: bool = True, alibi_slopes=None, kv_cache_dtype: str = "auto",
                               k_scale: float = 1.0, v_scale: float = 1.0, schedule: str = "auto",
-                              metric_schedule: str = "tile") -> None:
+                              metric_schedule: str = "tile", tree_mask: Optional[torch.Tensor] = None) -> None:
     """Attention of ``nq_s >= 0`` new tokens per sequence over the per-head paged cache (chunked prefill, a
     follow-up turn on a kept cache, prefix reuse, verifying draft tokens): ``query`` / ``out``
     ``[num_tokens, num_heads, head_size]`` packed over the sequences, sequence ``s`` owning tokens
@@ -737,13 +737,33 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     them behind it on the same stream, from the row statistics that entry left, by a kernel whose tile is 16 (token,
     query head) rows and that reads every K byte once for all rows (more than 64 rows raise; without ``metrics`` it
     changes nothing).  ``out`` has the same bits either way; the metric is the same rule summed in another order, fixed
-    and identical from run to run.  There is no ``"auto"``: ``"tile"`` is the default."""
+    and identical from run to run.  There is no ``"auto"``: ``"tile"`` is the default.
+
+    ``tree_mask`` (int64 ``[num_tokens]`` on the query's device): verify a draft TREE.  The new tokens see the whole
+    cached prefix but, among the new slots, only what their word says: with ``base = context_lens[s, h] - nq_s`` (signed)
+    token ``t`` sees slot ``i < context_lens[s, h]`` iff ``i < base`` or bit ``i - base`` of ``tree_mask[t]`` is set.  No
+    bit is implied (a token that sees itself has its own bit); the chain rule above is ``(1 << (j + 1)) - 1`` for token
+    ``j``, and gives the bits of the short / wide schedule.  For ``max_query_len <= 64`` and at most 64 (token, query
+    head) rows per KV head (more raise before anything is launched), every cache type and both block layouts, through
+    ``kvc_paged_attention_chunk_tree``: at most 32 rows run the tree variant of the short kernel, more that of the wide
+    kernel, so ``schedule`` must be ``"auto"``, ``"short"`` or ``"wide"`` -- the tile and split schedules have no tree
+    variant and raise.  ``metric_schedule`` may be either value: the metric always runs in row form behind the output
+    pass (the tile-form metric kernel has no tree variant), with "sees" read as above and the window test on the
+    ``query_positions`` the caller passes -- for a tree, depths.  Without ``tree_mask`` nothing changes."""
     if metric_schedule not in ("tile", "rows"):
         raise RuntimeError(f"paged_attention_kvc_chunk: metric_schedule {metric_schedule!r}: expected \"tile\" or \"rows\"")
     lib = _lib.load()
     if schedule not in ("auto", "tile", "short", "split", "wide"):
         raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r}: expected \"auto\", \"tile\", \"short\", "
                            "\"split\" or \"wide\"")
+    if tree_mask is not None:
+        if schedule in ("tile", "split"):
+            raise RuntimeError(f"paged_attention_kvc_chunk: schedule {schedule!r} has no tree variant: with tree_mask the "
+                               "short and wide kernels run (\"auto\", \"short\" or \"wide\")")
+        if not isinstance(tree_mask, torch.Tensor) or tree_mask.dtype != torch.int64:
+            raise RuntimeError("paged_attention_kvc_chunk: tree_mask must be an int64 tensor [num_tokens]")
+        if tree_mask.device != query.device or tree_mask.numel() != query.shape[0]:
+            raise RuntimeError("paged_attention_kvc_chunk: tree_mask must be an int64 tensor [num_tokens] on the query's device")
     kvds = {"auto": 0, "fp8": 1, "fp8_e4m3": 1, "fp8_e5m2": 2}
     if kv_cache_dtype not in kvds:
         raise RuntimeError(f"Unsupported data type of kv cache: {kv_cache_dtype}")
@@ -801,6 +821,21 @@ def paged_attention_kvc_chunk(out, query, key_cache, value_cache, num_kv_heads: 
     p.dtype, p.kv_cache_dtype = dtypes[query.dtype], kvds[kv_cache_dtype]
     p.use_l2 = int(bool(use_l2))
     p.block_layout = _lib.block_layout_id()
+    if tree_mask is not None:
+        if num_heads % p.num_kv_heads == 0 and not lib.kvc_paged_attention_chunk_tree_eligible(
+                p.num_heads, p.num_kv_heads, p.max_query_len):
+            raise RuntimeError("paged_attention_kvc_chunk: tree_mask takes max_query_len <= 64 and at most 64 (token, query "
+                               f"head) rows per KV head, this call has max_query_len {p.max_query_len} and "
+                               f"{p.max_query_len * (num_heads // p.num_kv_heads)} rows")
+        tm = _contig(tree_mask, keep)
+        pbytes = lib.kvc_paged_attention_chunk_short_workspace_bytes(num_seqs, num_heads, head_size, p.max_query_len,
+                                                                     p.max_context_len)
+        with on_device(query.device):
+            part = workspace(query.device, pbytes + 256, "attn_chunk_short")
+            _lib.check(lib.kvc_paged_attention_chunk_tree(p, tm.data_ptr(), float(k_scale), float(v_scale),
+                                                          part.data_ptr(), pbytes, _stream(query)))
+        _written(out, metrics)
+        return
     eligible = (lib.kvc_paged_attention_chunk_short_eligible if p.kv_cache_dtype == 0
                 else lib.kvc_paged_attention_chunk_short_fp8_eligible)
     short = schedule == "short" or (schedule == "auto" and bool(eligible(

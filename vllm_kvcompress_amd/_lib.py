@@ -15,7 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("KVC_MI355X_LIB", os.path.join(_HERE, "libkvc_mi355x.so"))
 
 MAX_INT = 2147483000  # reference vllm/kvcompress/metrics.py:12
-ABI_VERSION = 16    # KVC_ABI_VERSION of include/kvc_mi355x.h: the struct layouts mirrored below
+ABI_VERSION = 17   # KVC_ABI_VERSION of include/kvc_mi355x.h: the struct layouts mirrored below
 
 # KVC_LAYOUT_* of include/kvc_mi355x.h: how the bytes INSIDE a cache block are laid out.  The fork hands the ops
 # views of an opaque [2, NB, bs * hd] tensor (reference vllm/attention/ops/paged_attn.py:262-284); the three ops that
@@ -252,6 +252,9 @@ SYMBOLS = {
     "kvc_paged_attention_chunk_wide_fp8": (c_int32, [ctypes.POINTER(KvcAttentionChunkParams), c_float, c_float, c_void_p,
                                                      c_size_t, c_void_p]),
     "kvc_paged_attention_chunk_metric_rows": (c_int32, [ctypes.POINTER(KvcAttentionChunkParams), c_float, c_void_p]),
+    "kvc_paged_attention_chunk_tree_eligible": (c_int32, [c_int32, c_int32, c_int32]),
+    "kvc_paged_attention_chunk_tree": (c_int32, [ctypes.POINTER(KvcAttentionChunkParams), c_void_p, c_float, c_float,
+                                                 c_void_p, c_size_t, c_void_p]),
 }
 
 _lib = None

@@ -10,7 +10,7 @@ OBJ="$(mktemp -d "${TMPDIR:-/tmp}/kvc_build.XXXXXX")"
 trap 'rm -rf "$OBJ"' EXIT
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-value ${KVC_EXTRA_FLAGS:-}"
 pids=()
-for src in kvc_api kvc_moves kvc_compact kvc_schedule kvc_aggregate kvc_blockstate kvc_attention kvc_attention_inst_f16 kvc_attention_inst_bf16 kvc_attention_inst_fp8_f16 kvc_attention_inst_fp8_bf16 kvc_prefill_attn kvc_attention_chunk kvc_attention_chunk_fp8 kvc_attention_chunk_short kvc_attention_chunk_short_fp8 kvc_attention_chunk_split kvc_attention_chunk_split_fp8 kvc_attention_chunk_wide kvc_attention_chunk_wide_fp8 kvc_attention_chunk_metric_rows kvc_attention_chunk_metric_rows_fp8; do
+for src in kvc_api kvc_moves kvc_compact kvc_schedule kvc_aggregate kvc_blockstate kvc_attention kvc_attention_inst_f16 kvc_attention_inst_bf16 kvc_attention_inst_fp8_f16 kvc_attention_inst_fp8_bf16 kvc_prefill_attn kvc_attention_chunk kvc_attention_chunk_fp8 kvc_attention_chunk_short kvc_attention_chunk_short_fp8 kvc_attention_chunk_split kvc_attention_chunk_split_fp8 kvc_attention_chunk_wide kvc_attention_chunk_wide_fp8 kvc_attention_chunk_metric_rows kvc_attention_chunk_metric_rows_fp8 kvc_attention_chunk_tree kvc_attention_chunk_tree_fp8; do
   "$HIPCC" $FLAGS -c "$HERE/$src.hip" -o "$OBJ/$src.o" &
   pids+=($!)
 done

@@ -96,6 +96,23 @@ struct HeadView {
   __device__ __forceinline__ int limit(int j) const { return max(0, ctx - (nq - 1 - j)); }
 };
 
+// The tree rule of the TREE kernel variants (kvc_attention_chunk_tree.hip): with base = ctx - nq (signed), a token
+// with mask word W sees slot i < ctx iff e = i - base < 0 (the cached prefix) or bit e of W is set (e < nq: one of
+// the new tokens).  tree_word clears the bits from nq up, so that a set bit alone says "a slot below ctx".
+__device__ __forceinline__ uint64_t tree_word(const uint64_t* tree, int idx, int nq) {
+  const uint64_t wd = tree[idx];
+  return nq >= 64 ? wd : wd & ((1ull << (nq & 63)) - 1ull);
+}
+// The rule for 32 consecutive slots at once: bit b says whether a token with (cleared) word W sees the slot with
+// e = e0 + b -- ones below e = 0, the word's bits from there, zeros from e = 64.  A lane's keys of a step lie within
+// 20 slots, so one 64-bit shift serves all its weights.  Every shift amount is masked behind the compare that bounds
+// it: never the operand's width or more.
+__device__ __forceinline__ uint32_t tree_window(uint64_t word, int e0) {
+  if (e0 <= -32) return 0xFFFFFFFFu;
+  if (e0 < 0) return (uint32_t)(word << (-e0 & 31)) | ((1u << (-e0 & 31)) - 1u);      // -e0 = 1 .. 31
+  return e0 < 64 ? (uint32_t)(word >> (e0 & 63)) : 0u;
+}
+
 // ---------------------------------------------------------------------------------- 1. output pass
 template <typename T, int HD, int NT, int KVD>
 __global__ __launch_bounds__(256) void chunk_out_kernel(ChunkArgs a) {

@@ -6,6 +6,8 @@
 #pragma once
 #include "kvc_attention_chunk.h"
 
+#include <type_traits>
+
 namespace kvc {
 
 // the fp8 instantiations' side of kvc_paged_attention_chunk_metric_rows (kvc_attention_chunk_metric_rows_fp8.hip)
@@ -22,6 +24,11 @@ struct MetricRowsArgs {
   ChunkArgs c;
   int32_t mpl, use_l2;             // partition length (128 * 2^k slots), sum p^2 or sum p
 };
+// the TREE variant's arguments (kvc_attention_chunk_tree.hip): the chain kernel's argument block stays what it is
+struct MetricRowsTreeArgs : MetricRowsArgs {
+  const uint64_t* tree;            // [num_tokens]: bit e of token t = t sees the sequence's e-th new slot
+};
+template <bool TREE> using MetricRowsArgsOf = std::conditional_t<TREE, MetricRowsTreeArgs, MetricRowsArgs>;
 
 // The partition length: the longest 128 * 2^k in [MR_PL_MIN, MR_PL_MAX] that still leaves MR_GRID workgroups.  Every
 // slot's sum is formed inside ONE 32-key step of one wave, and the steps start at multiples of 32 whatever the
@@ -32,8 +39,11 @@ inline int metric_rows_partition(int64_t max_ctx, int64_t heads_x_seqs) {
   return mpl;
 }
 
-template <typename T, int HD, int NT, bool SM, int KVD>
-__global__ __launch_bounds__(256) void chunk_metric_rows_kernel(MetricRowsArgs x) {
+// TREE: "sees" is the tree rule (kvc_attention_chunk.h).  A lane keeps the mask word of its row where the chain keeps
+// the row's limit (padding rows: a base that puts every key past the word), and the wave-uniform skip asks the OR of
+// a tile's words -- "no row of the tile sees these 16 keys" -- where the chain asks the tile's largest limit.
+template <typename T, int HD, int NT, bool SM, int KVD, bool TREE = false>
+__global__ __launch_bounds__(256) void chunk_metric_rows_kernel(MetricRowsArgsOf<TREE> x) {
   using M = Mma16<T>;
   using V8 = typename M::V8;
   constexpr bool F8 = KVD != 0, E5M2 = KVD == 2;
@@ -45,7 +55,8 @@ __global__ __launch_bounds__(256) void chunk_metric_rows_kernel(MetricRowsArgs x
   const int s = blockIdx.z, hk = blockIdx.y;
   const HeadView hv(a, s, hk);
   if (hv.nq <= 0) return;
-  const int lim_max = hv.limit(hv.nq - 1);                       // the last token sees the most
+  const int base = hv.ctx - hv.nq;                               // TREE: the first new slot (signed)
+  const int lim_max = TREE ? hv.ctx : hv.limit(hv.nq - 1);       // the last token sees the most (TREE: nobody sees more)
   const int kp0 = blockIdx.x * x.mpl;
   if (kp0 >= lim_max) return;
   const int part_end = min(kp0 + x.mpl, lim_max);
@@ -63,12 +74,26 @@ __global__ __launch_bounds__(256) void chunk_metric_rows_kernel(MetricRowsArgs x
   // k-step ks contracts dims 16 (g + 4 (ks / 2)) + 8 (ks % 2) ..  Padding rows: zero Q, limit 0.
   V8 bq[NT][KS];
   int vis[NT], win[NT], tile_lim[NT];
+  int rbase[TREE ? NT : 1];                                      // TREE: instead of vis and tile_lim
+  uint64_t word[TREE ? NT : 1], tile_or[TREE ? NT : 1];
   float rmax[NT], rinv[NT];
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int r = 16 * nt + c, tok = r / a.qpk, hq = r - tok * a.qpk;
     const bool ok = r < nrows;
-    vis[nt] = ok ? hv.limit(tok) : 0;
+    if constexpr (TREE) {
+      // a padding row's base makes e = key - base >= 2^30 for every key: past the word, never below 0
+      rbase[nt] = ok ? base : -(1 << 30);
+      vis[nt] = 0;
+      word[nt] = ok ? tree_word(x.tree, hv.q0 + tok, hv.nq) : 0ull;
+      // (wave-uniform) the OR over the tokens of the tile's rows
+      tile_or[nt] = 0ull;
+      if (16 * nt < nrows)
+        for (int tt = 16 * nt / a.qpk; tt <= (min(nrows, 16 * nt + 16) - 1) / a.qpk; ++tt)
+          tile_or[nt] |= tree_word(x.tree, hv.q0 + tt, hv.nq);
+    } else {
+      vis[nt] = ok ? hv.limit(tok) : 0;
+    }
     win[nt] = ok ? a.qpos[hv.q0 + tok] - a.buf_len[s] : (int)0x80000000;
     rmax[nt] = rinv[nt] = 0.0f;
     if (ok) {
@@ -148,14 +173,25 @@ __global__ __launch_bounds__(256) void chunk_metric_rows_kernel(MetricRowsArgs x
       // row tiles ascending: the order of a slot's sum inside the lane
 #pragma unroll
       for (int nt = 0; nt < NT; ++nt) {
-        if (tile_lim[nt] <= k0 + 16 * h) continue;               // (wave-uniform) no row of the tile sees these keys
+        // (wave-uniform) no row of the tile sees these keys
+        if constexpr (TREE) {
+          const int e0 = k0 + 16 * h - base;                     // >= 0: the half lies in the new slots; e0 < nq <= 64 there
+          if (16 * nt >= nrows || (e0 >= 0 && (e0 >= hv.nq || ((tile_or[nt] >> (e0 & 63)) & 0xFFFFull) == 0ull))) continue;
+        } else {
+          if (tile_lim[nt] <= k0 + 16 * h) continue;
+        }
         cf32x4 sa = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) sa = M::mma(ak[ks], bq[nt][ks], sa);
+        uint32_t seen = 0u;                                      // TREE: bit i = the row sees key k0 + 16 h + 4 g + i
+        if constexpr (TREE) seen = tree_window(word[nt], k0 + 16 * h + 4 * g - rbase[nt]);
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
           const int j = 4 * h + i;
-          const bool pass = k0 + 16 * h + 4 * g + i < vis[nt] && r.pos[j] <= win[nt];
+          bool sees;
+          if constexpr (TREE) sees = (seen >> i) & 1u;
+          else sees = k0 + 16 * h + 4 * g + i < vis[nt];
+          const bool pass = sees && r.pos[j] <= win[nt];
           const float p = pass ? __builtin_amdgcn_exp2f(sa[i] * sc - rmax[nt]) * rinv[nt] : 0.0f;
           acc[j] = __builtin_fmaf(p, l2 ? p : 1.0f, acc[j]);
           touched |= (pass ? 1u : 0u) << j;

@@ -7,6 +7,8 @@
 #pragma once
 #include "kvc_attention_chunk.h"
 
+#include <type_traits>
+
 namespace kvc {
 namespace {
 
@@ -20,9 +22,17 @@ struct ShortArgs {
   float* pml;                      // partial (m, l)  [num_seqs][nparts][num_kv_heads][rows][2]
   int32_t pl, nparts, rows;        // partition length, partitions of max_ctx, max_q * qpk
 };
+// the TREE variants' arguments (kvc_attention_chunk_tree.hip): the chain kernels' argument block stays what it is
+struct ShortTreeArgs : ShortArgs {
+  const uint64_t* tree;            // [num_tokens]: bit e of token t = t sees the sequence's e-th new slot
+};
+template <bool TREE> using ShortArgsOf = std::conditional_t<TREE, ShortTreeArgs, ShortArgs>;
 
-template <typename T, int HD, int NT, bool SM, int KVD>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void chunk_short_kernel(ShortArgs x) {
+// TREE: the rows' visibility is the tree rule (kvc_attention_chunk.h) instead of the chain's limits -- every row sees
+// the whole prefix, the mask runs on the steps that reach the last nq slots, and a lane keeps the 64-bit word of its
+// row 16 nt + c where the chain keeps lim[nt]
+template <typename T, int HD, int NT, bool SM, int KVD, bool TREE = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void chunk_short_kernel(ShortArgsOf<TREE> x) {
   using M = Mma16<T>;
   using V8 = typename M::V8;
   constexpr bool F8 = KVD != 0, E5M2 = KVD == 2;
@@ -44,7 +54,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const int s = blockIdx.z, hk = blockIdx.y;
   const HeadView hv(a, s, hk);
   if (hv.nq <= 0) return;                                        // (uniform: before any barrier)
-  const int lim_max = hv.limit(hv.nq - 1), lim_min = hv.limit(0);
+  const int base = hv.ctx - hv.nq;                               // TREE: the first new slot (signed)
+  const int lim_max = TREE ? hv.ctx : hv.limit(hv.nq - 1), lim_min = TREE ? base : hv.limit(0);
   const int kp0 = blockIdx.x * x.pl;
   if (x.nparts > 1 && kp0 >= lim_max) return;                    // the combine never looks at this partition
   const int part_end = min(kp0 + x.pl, lim_max);
@@ -62,12 +73,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // Q operands of row 16 nt + c.  2-byte caches: dims 32 ks + 8 g ..  fp8: a lane's 16-byte K read (dims 16 (g + 4 x)
   // ..) feeds k-steps 2 x and 2 x + 1 with its two halves, so k-step ks contracts dims 16 (g + 4 (ks / 2)) + 8 (ks % 2) ..
   V8 bq[NT][KS];
-  int lim[NT];
+  int lim[TREE ? 1 : NT];
+  uint64_t word[TREE ? NT : 1];                                  // TREE: the row's mask word, 0 for padding rows
 #pragma unroll
   for (int nt = 0; nt < NT; ++nt) {
     const int r = 16 * nt + c, tok = r / a.qpk, hq = r - tok * a.qpk;
     const bool ok = r < nrows;
-    lim[nt] = ok ? hv.limit(tok) : 0;
+    if constexpr (TREE) word[nt] = ok ? tree_word(x.tree, hv.q0 + tok, hv.nq) : 0ull;
+    else lim[nt] = ok ? hv.limit(tok) : 0;
     const T* qp = reinterpret_cast<const T*>(a.q) + (int64_t)(hv.q0 + tok) * a.q_stride + (int64_t)(hk * a.qpk + hq) * HD +
                   (F8 ? 16 : 8) * g;
 #pragma unroll
@@ -211,6 +224,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   const float sc = a.scale * CH_LOG2E;
   // the key (within the step) of weight j of a lane: fp8 reference blocks number the rows of QK^T differently (load)
   auto key_of = [&](int j) { return (F8 && !SM) ? 8 * g + j : 16 * (j >> 2) + 4 * g + (j & 3); };
+  // TREE, masked steps: bit key_of(j) - key_of(0) says whether row 16 nt + c sees the key of weight j
+  auto step_window = [&](int nt, bool masked, int k0) -> uint32_t {
+    if constexpr (TREE) {
+      return masked ? tree_window(word[nt], k0 + key_of(0) - base) : 0u;
+    } else {
+      return 0u;
+    }
+  };
+  // row 16 nt + c does not see the key of weight j (asked on masked steps only)
+  auto hidden = [&](int nt, uint32_t win, int j, int k0) {
+    if constexpr (TREE) return ((win >> (key_of(j) - key_of(0))) & 1u) == 0u;
+    else return k0 + key_of(j) >= lim[nt];
+  };
 
   auto compute = [&](const Raw& r, const Raw& rv, int k0) {
     // S^T, one half (16 keys) at a time: the K operands of a half are dead before the next half's are made
@@ -277,10 +303,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
       for (int nt = 0; nt < NT; ++nt) {
         if (16 * nt >= nrows) continue;
         float tv[8], tmax = -INFINITY;
+        const uint32_t win = step_window(nt, masked, k0);
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           float t = sa[nt][j >> 2][j & 3] * sc;
-          if (masked && k0 + key_of(j) >= lim[nt]) t = -INFINITY;
+          if (masked && hidden(nt, win, j, k0)) t = -INFINITY;
           tv[j] = t;
           tmax = fmaxf(tmax, t);
         }
@@ -342,10 +369,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     for (int nt = 0; nt < NT; ++nt) {
       if (16 * nt >= nrows) continue;
       float tv[8], tmax = -INFINITY;
+      const uint32_t win = step_window(nt, masked, k0);
 #pragma unroll
       for (int j = 0; j < 8; ++j) {                              // key k0 + 16 (j / 4) + 4 g + j % 4 of row c
         float t = sa[nt][j >> 2][j & 3] * sc;
-        if (masked && k0 + 16 * (j >> 2) + 4 * g + (j & 3) >= lim[nt]) t = -INFINITY;
+        if (masked && hidden(nt, win, j, k0)) t = -INFINITY;
         tv[j] = t;
         tmax = fmaxf(tmax, t);
       }

@@ -10,8 +10,10 @@ namespace {
 
 constexpr int CW_MAX_ROWS = 64;    // (token, query head) rows per KV head: four MFMA tiles
 
-template <typename T, int HD, int NT, bool SM>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void chunk_wide_kernel(ShortArgs x) {
+// TREE: the tree rule (kvc_attention_chunk.h) instead of the chain's limits; the rows' mask words sit in an LDS tile
+// where the chain keeps slim, read on masked steps only
+template <typename T, int HD, int NT, bool SM, bool TREE = false>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) void chunk_wide_kernel(ShortArgsOf<TREE> x) {
   using M = Mma16<T>;
   using V8 = typename M::V8;
   constexpr int KS = HD / 32;                 // MFMA k-steps of QK^T
@@ -31,13 +33,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
   // the Q tile, then (slot-major) the waves' K tiles; after the key loop the merged O over both
   __shared__ __attribute__((aligned(16))) uint8_t lds[LB];
   __shared__ float sm[4][NR], sl[4][NR], rM[NR], rL[NR];
-  __shared__ int slim[NR];                                       // the rows' causal limits: read on masked steps only
+  __shared__ int slim[TREE ? 1 : NR];                            // the rows' causal limits: read on masked steps only
+  __shared__ uint64_t stree[TREE ? NR : 1];                      // TREE: the rows' mask words instead
 
   const ChunkArgs& a = x.c;
   const int s = blockIdx.z, hk = blockIdx.y;
   const HeadView hv(a, s, hk);
   if (hv.nq <= 0) return;                                        // (uniform: before any barrier)
-  const int lim_max = hv.limit(hv.nq - 1), lim_min = hv.limit(0);
+  const int base = hv.ctx - hv.nq;                               // TREE: the first new slot (signed)
+  const int lim_max = TREE ? hv.ctx : hv.limit(hv.nq - 1), lim_min = TREE ? base : hv.limit(0);
   const int kp0 = blockIdx.x * x.pl;
   if (x.nparts > 1 && kp0 >= lim_max) return;                    // the combine never looks at this partition
   const int part_end = min(kp0 + x.pl, lim_max);
@@ -66,7 +70,11 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
     if (rr >= NR) rr -= NR;
     *reinterpret_cast<cu32x4*>(lds + (pc * NR + rr) * 16) = raw;
   }
-  if (tid < NR) slim[tid] = tid < nrows ? hv.limit(tid / a.qpk) : 0;
+  if constexpr (TREE) {
+    if (tid < NR) stree[tid] = tid < nrows ? tree_word(x.tree, hv.q0 + tid / a.qpk, hv.nq) : 0ull;
+  } else {
+    if (tid < NR) slim[tid] = tid < nrows ? hv.limit(tid / a.qpk) : 0;
+  }
   // byte offset of (piece g, row 16 nt + c) in the Q tile: only the last row tile can wrap
   const int qrow = c + 4 * g, qbase = (g * NR + qrow) * 16;
   auto qoff = [&](int nt) { return qbase + (nt == NT - 1 && qrow >= 16 ? 16 * nt - NR : 16 * nt) * 16; };
@@ -208,10 +216,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
         tv[j] = sa[j >> 2][j & 3] * sc;
       }
       if (masked) {                                              // (uniform: the last steps of a head only)
-        const int left = slim[16 * nt + c] - k0 - 4 * g;         // key 16 (j / 4) + 4 g + j % 4 of the step is weight j
+        if constexpr (TREE) {
+          // weight j is the new slot e0 + 16 (j / 4) + j % 4 with e0 = k0 + 4 g - base (the prefix: below 0)
+          const uint32_t win = tree_window(stree[16 * nt + c], k0 + 4 * g - base);
 #pragma unroll
-        for (int j = 0; j < 8; ++j)
-          if (16 * (j >> 2) + (j & 3) >= left) tv[j] = -INFINITY;
+          for (int j = 0; j < 8; ++j)
+            if (((win >> (16 * (j >> 2) + (j & 3))) & 1u) == 0u) tv[j] = -INFINITY;
+        } else {
+          const int left = slim[16 * nt + c] - k0 - 4 * g;       // key 16 (j / 4) + 4 g + j % 4 of the step is weight j
+#pragma unroll
+          for (int j = 0; j < 8; ++j)
+            if (16 * (j >> 2) + (j & 3) >= left) tv[j] = -INFINITY;
+        }
       }
 #pragma unroll
       for (int j = 0; j < 8; ++j) tmax = fmaxf(tmax, tv[j]);
